@@ -2,6 +2,7 @@
 """Benchmark of the batched quorum engine (BASELINE.json metric).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+                  [--dump-outputs DIR] [--full]
 
 One step = one pass of the hot path over this rank's resident batch.  The
 headline workload (default, BASELINE configs[1]) is 64M groups x 5-voter
@@ -9,9 +10,11 @@ MajorityConfig CommittedIndex + VoteResult (+ TallyVotes counts) per GPU;
 groups are sharded across ranks (weak scaling, no data-path collective; one
 RCCL all-reduce of the statistics vector after the timed region).
 
-Rank 0 prints ONE JSON line with the metric, the roofline of the dominant
-kernel (HIP events on the launch stream), and the CPU baseline (oracle port,
-rank 0 at N=1 only, bounded sample).
+Rank 0 prints ONE JSON line with the metric and the roofline of the dominant
+kernel (HIP events on the launch stream).  A plain run times the chosen
+workload alone; --full adds the secondary workloads (`aux`) and the CPU
+baseline (oracle port, rank 0 at N=1 only, bounded sample).  --dump-outputs
+DIR writes what the last timed step computed as DIR/<name>.npy (dump_outputs).
 """
 import argparse
 import json
@@ -108,8 +111,16 @@ def parse(argv=None):
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="config2_n5", choices=sorted(WORKLOADS))
     ap.add_argument("--groups", type=int, default=0, help="override groups per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-aux", action="store_true", help="skip the secondary workloads")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the secondary "
+                         "workloads (aux) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as "
+                         "DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-aux", action="store_true",
+                    help="with --full: skip the secondary workloads")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="CPU baseline threads (0 = this process's CPU share: the affinity "
                          "set, capped by OMP_NUM_THREADS when the box sets it)")
@@ -550,7 +561,8 @@ def setup(name, G, S, kind, d, stats):
                 u += (uni >> s) & 1
             mean_u = float(u.double().mean().item())
             bpg = 3 * 2 + 2 * 2 + 8 * mean_u + 9
-        return step, bpg, G, "group-evals", {"batch": b, "out": out}
+        return step, bpg, G, "group-evals", {
+            "batch": b, "out": out, "outputs": {"commit": out.commit, "vote": out.vote}}
     if kind in ("repl", "repl_joint"):
         joint = kind == "repl_joint"
         b = engine.SlotBatch(G, S, d.dev, masks=("inc", "out") if joint else (), votes=False,
@@ -615,8 +627,10 @@ def setup(name, G, S, kind, d, stats):
                           int((st.committed != pristine["committed"]).sum())) + G
             prepare()
         bpg = 2 + 24 + 8 * S + 16 * nresp + writes / G + (2 if joint else 0)  # + inc/out masks
-        return step, bpg, G, "group-rounds", {"b": b, "st": st, "resp": resp,
-                                               "prepare": prepare}
+        return step, bpg, G, "group-rounds", {
+            "b": b, "st": st, "resp": resp, "prepare": prepare,
+            "outputs": {"match": b.match, "next": st.next, "committed": st.committed,
+                        "read_ok": read_ok}}
     if kind in ("elec", "elec_pvcq"):
         # config 5; elec_pvcq: raft.Config{PreVote, CheckQuorum} with each
         # peer heard from within an election timeout with p = 0.7
@@ -642,7 +656,10 @@ def setup(name, G, S, kind, d, stats):
 
         # HBM bytes per group-step: state in+out / steps (register-resident)
         bpg = (8 + 1 + 1 + 1 + 1 + 1 + 8 + 1 + 1 + 1) / steps_per_launch
-        return step, bpg, G * steps_per_launch, "group-steps", {"b": b, "est": est}
+        return step, bpg, G * steps_per_launch, "group-steps", {
+            "b": b, "est": est,
+            "outputs": {"term": est.term, "state": est.state, "voted": est.voted,
+                        "granted": est.granted}}
     if kind in ("progress", "progress_joint"):
         F, R, ME = 8, int(os.environ.get("QE_BENCH_RUNS", "4")), 16  # R: A/B knob only
         joint = kind == "progress_joint"
@@ -696,7 +713,12 @@ def setup(name, G, S, kind, d, stats):
             engine.check("qe_progress_step",
                          lib.qe_progress_step(C.byref(p_), C.byref(m_), sp, stream))
 
-        return step, bpg, G, "group-rounds", {"ps": ps, "msgs": msgs, "prepare": prepare}
+        return step, bpg, G, "group-rounds", {
+            "ps": ps, "msgs": msgs, "prepare": prepare,
+            "outputs": {"match": ps.match, "next": ps.next, "pending": ps.pending,
+                        "peer": ps.peer, "committed": ps.committed, "sent": msgs.sent,
+                        "bcast": msgs.bcast, "msg_count": msgs.msg_count,
+                        "msg_index": msgs.msg_index}}
     if kind == "propose":
         # stepLeader MsgProp -> appendEntry -> bcastAppend (raft/raft.go:
         # 1019-1076, :621-642, :515-522) on the progress_send state, the
@@ -739,8 +761,12 @@ def setup(name, G, S, kind, d, stats):
         def verify():
             return bool((pr.result == 1).all())
 
-        return step, bpg, G, "group-proposals", {"ps": ps, "pr": pr, "prepare": prepare,
-                                                 "verify": verify}
+        return step, bpg, G, "group-proposals", {
+            "ps": ps, "pr": pr, "prepare": prepare, "verify": verify,
+            "outputs": {"match": ps.match, "next": ps.next, "peer": ps.peer,
+                        "committed": ps.committed, "last_index": ps.last_index,
+                        "uncommitted_size": pr.uncommitted_size, "result": pr.result,
+                        "sent": pr.sent, "snap": pr.snap}}
 
     if kind == "switch":
         # raft.switchToConfig (raft/raft.go:1651-1700) on the progress_send
@@ -792,8 +818,11 @@ def setup(name, G, S, kind, d, stats):
             out = sw.result & engine._lib.QE_SW_OUTCOME
             return bool(((out == engine._lib.QE_SW_BCAST) | (out == engine._lib.QE_SW_PROBE)).all())
 
-        return step, bpg, G, "group-switches", {"ps": ps, "sw": sw, "prepare": prepare,
-                                                "verify": verify}
+        return step, bpg, G, "group-switches", {
+            "ps": ps, "sw": sw, "prepare": prepare, "verify": verify,
+            "outputs": {"next": ps.next, "peer": ps.peer, "committed": ps.committed,
+                        "lead_transferee": ps.lead_transferee, "result": sw.result,
+                        "sent": sw.sent, "snap": sw.snap}}
 
     if kind == "heartbeat":
         # stepLeader MsgBeat -> bcastHeartbeat -> sendHeartbeat (raft/raft.go:
@@ -832,8 +861,9 @@ def setup(name, G, S, kind, d, stats):
             return (bool((sent.to(torch.int32) == full).all()) and bool((c == want).all())
                     and bool((ctx.to(torch.int64) & 0xFFFFFFFF == cx).all()))
 
-        return step, bpg, G, "group-heartbeats", {"ps": ps, "commit": commit, "ctx": ctx,
-                                                  "sent": sent, "verify": verify}
+        return step, bpg, G, "group-heartbeats", {
+            "ps": ps, "commit": commit, "ctx": ctx, "sent": sent, "verify": verify,
+            "outputs": {"commit": commit, "ctx": ctx, "sent": sent}}
 
     if kind == "psend":
         # raft.appendEntry -> bcastAppend (raft/raft.go:515-522, :432-492):
@@ -869,8 +899,9 @@ def setup(name, G, S, kind, d, stats):
         # 131 B, or 123 B
         nw = bin(full & ~1).count("1")
         bpg = 1 + 16 + 2 + nw * (12 + 12 + (2 if RING16 else 4))
-        return step, bpg, G, "group-bcasts", {"ps": ps, "prepare": prepare,
-                                              "t": (want, sent, snap)}
+        return step, bpg, G, "group-bcasts", {
+            "ps": ps, "prepare": prepare, "t": (want, sent, snap),
+            "outputs": {"next": ps.next, "peer": ps.peer, "sent": sent, "snap": snap}}
     if kind == "cq":
         ps = engine.ProgressState(G, S, 1, 1, d.dev, group_offset=goff, extras=("self_slot",))
         act = counter_rows(G, S, 0xC4EC, goff, d.dev, ps.stride) % 10 < 7  # heard from within the timeout
@@ -901,7 +932,9 @@ def setup(name, G, S, kind, d, stats):
         changed = int((ps.peer.view(S, ps.stride)[:, :G] != pristine.view(S, ps.stride)[:, :G]).sum())
         prepare()
         bpg = 1 + 4 * S + 1 + 4 * changed / G
-        return step, bpg, G, "group-checks", {"ps": ps, "prepare": prepare, "t": qa}
+        return step, bpg, G, "group-checks", {
+            "ps": ps, "prepare": prepare, "t": qa,
+            "outputs": {"peer": ps.peer, "quorum_active": qa}}
     if kind == "collect":
         gen = torch.Generator(device=d.dev).manual_seed(0xC011 + d.rank)
         flags = (torch.rand(G, device=d.dev, generator=gen) < 0.5).to(torch.uint8)
@@ -926,7 +959,9 @@ def setup(name, G, S, kind, d, stats):
         # every flag read once; per selected group its value read and the id
         # and value written (8 + 16 B)
         bpg = 1 + 24 * sel / G
-        return step, bpg, G, "groups", {"t": (flags, values, scratch, groups, vals, count)}
+        return step, bpg, G, "groups", {
+            "t": (flags, values, scratch, groups, vals, count),
+            "outputs": {"groups": groups[:sel], "values": vals[:sel], "count": count}}
     if kind == "confchange":
         cs = engine.ConfState(G, S, d.dev)
         ps = engine.ProgressState(G, S, 1, 1, d.dev)
@@ -974,8 +1009,11 @@ def setup(name, G, S, kind, d, stats):
             ok = bool((ch.result == 0).all()) and bool((cs.inc == 0b01111).all())
             return ok and bool((cs.learner == 0b10000).all())
 
-        return step, bpg, G, "group-changes", {"cs": cs, "ps": ps, "ch": ch,
-                                               "prepare": prepare, "verify": verify}
+        return step, bpg, G, "group-changes", {
+            "cs": cs, "ps": ps, "ch": ch, "prepare": prepare, "verify": verify,
+            "outputs": {"slot_ids": cs.slot_ids, "inc": cs.inc, "learner": cs.learner,
+                        "is_learner": cs.is_learner, "tracked": cs.tracked,
+                        "result": ch.result}}
     raise ValueError(kind)
 
 
@@ -1001,6 +1039,52 @@ def time_steps(step, d, steps, warmup, prepare=None):
     wall = time.perf_counter() - t0
     kern_ms = [a.elapsed_time(b) for a, b in evs]
     return wall, kern_ms
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # of the 64 MB a dump may take
+DUMP_SEED = 0xD0C5
+
+
+def _dump_arrays(name, a):
+    """{file stem: float array} holding integer array `a` exactly: 64-bit
+    words as their high and low 32-bit halves in float64, 32-bit words in
+    float64, narrower ones in float32."""
+    if a.dtype.kind == "f":
+        return {name: a.astype(np.float64 if a.itemsize > 4 else np.float32)}
+    if a.dtype.kind == "b":
+        return {name: a.astype(np.float32)}
+    if a.itemsize == 8:
+        u = a.view(np.uint64)
+        return {f"{name}_hi32": (u >> np.uint64(32)).astype(np.float64),
+                f"{name}_lo32": (u & np.uint64(0xFFFFFFFF)).astype(np.float64)}
+    return {name: a.astype(np.float64 if a.itemsize == 4 else np.float32)}
+
+
+def dump_outputs(path, outputs, rank=0, world=1):
+    """--dump-outputs: write the tensors in `outputs` (what the last timed
+    step left in HBM) under `path` as <name>.npy (rank r > 0 of a multi-rank
+    run: <name>.rank<r>.npy).  A tensor of more than k elements is written as
+    a sample of k of them, the same k for every tensor: the flat positions
+    sorted(default_rng(DUMP_SEED).integers(0, numel, k)), a function of the
+    tensor's size alone, so two runs with the same arguments write the same
+    elements.  k is the largest power of two at which the files fit
+    DUMP_BUDGET_BYTES."""
+    os.makedirs(path, exist_ok=True)
+    outputs = {n: t.reshape(-1) for n, t in outputs.items() if t is not None}
+    cost = lambda t: 16 if t.element_size() == 8 else 8 if t.element_size() == 4 else 4  # noqa: E731
+    k = 1 << 30
+    while k > 1 and sum(min(t.numel(), k) * cost(t) for t in outputs.values()) > DUMP_BUDGET_BYTES:
+        k >>= 1
+    index = {}
+    for name, t in outputs.items():
+        n = t.numel()
+        if n > k:
+            if n not in index:
+                pos = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, k))
+                index[n] = torch.from_numpy(pos).to(t.device)
+            t = t[index[n]]
+        for stem, a in _dump_arrays(name, t.cpu().numpy()).items():
+            np.save(os.path.join(path, stem + (f".rank{rank}" if rank else "") + ".npy"), a)
 
 
 def cpu_model():
@@ -1165,7 +1249,7 @@ def valu_roofline(workload, kern_ms, units):
     return out
 
 
-def run_workload(name, args, d, steps, warmup):
+def run_workload(name, args, d, steps, warmup, dump=None):
     desc, G, S, kind = WORKLOADS[name]
     if args.groups and name == args.workload:
         G = args.groups
@@ -1179,6 +1263,9 @@ def run_workload(name, args, d, steps, warmup):
     if keep.get("verify"):
         torch.cuda.synchronize(d.dev)
         assert keep["verify"](), f"{name}: unexpected result"
+    if dump:
+        torch.cuda.synchronize(d.dev)
+        dump_outputs(dump, keep["outputs"], d.rank, d.world)
     kern_avg = d.max(float(np.mean(kern_ms)))
     # with a per-launch state restore the wall clock also holds the restore
     # copies: the step time is then the launch's own HIP-event time
@@ -1336,9 +1423,9 @@ def main():
         # each gets its share of this process's CPUs, not all of them
         local = int(os.environ.get("LOCAL_WORLD_SIZE", str(d.world)))
         engine._lib.lib().qe_pack_threads(max(1, cpu_share() // max(1, local)))
-    main_res = run_workload(args.workload, args, d, args.steps, args.warmup)
+    main_res = run_workload(args.workload, args, d, args.steps, args.warmup, args.dump_outputs)
     aux = {}
-    if not args.no_aux:
+    if args.full and not args.no_aux:
         aux["config1_n3"] = config1(args, d)
         aux["config2_n5_pcie"] = pcie_inclusive(args, d)
         for name in WORKLOADS:
@@ -1352,7 +1439,7 @@ def main():
                     aux[name][k] = r[k]
 
     cpu = None
-    if d.rank == 0 and d.world == 1 and not args.no_cpu_baseline:
+    if args.full and d.rank == 0 and d.world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args)
     if d.rank == 0:
         desc, G, S, kind = WORKLOADS[args.workload]

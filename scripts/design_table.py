@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""DESIGN.md §6's measurement table from one bench log and the committed PMC:
+"""DESIGN.md §6's measurement table from one bench log (of a `bench.py --full`
+run: the rows are its aux workloads) and the committed PMC:
 
   python scripts/design_table.py profiles/r05/bench_fin.log [profiles/r05_pmc.json]
 

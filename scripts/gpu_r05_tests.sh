@@ -10,7 +10,7 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -q -p no:cacheprovider ${P
   --timeout 120 --timeout-method thread > "$O/gpu_tests.log" 2>&1 || { echo "gpu tests failed"; tail -40 "$O/gpu_tests.log"; exit 3; }
 tail -2 "$O/gpu_tests.log"
 if [ "${BENCH:-1}" = 1 ]; then
-  timeout -k 10 600 python -u bench.py ${BENCH_ARGS:-} > "$O/bench.log" 2>&1 || { echo bench failed; tail -20 "$O/bench.log"; exit 4; }
+  timeout -k 10 600 python -u bench.py --full ${BENCH_ARGS:-} > "$O/bench.log" 2>&1 || { echo bench failed; tail -20 "$O/bench.log"; exit 4; }
   tail -1 "$O/bench.log" | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())

@@ -11,7 +11,7 @@ if [ "${TESTS:-1}" = 1 ]; then
   timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1 || { echo smoke failed; tail -20 "$O/smoke.log"; exit 3; }
   tail -1 "$O/smoke.log"
 fi
-timeout -k 10 600 python -u bench.py --gpus 1 --steps 20 --warmup 5 > "$O/bench.log" 2>&1 || { echo bench failed; tail -20 "$O/bench.log"; exit 4; }
+timeout -k 10 600 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 > "$O/bench.log" 2>&1 || { echo bench failed; tail -20 "$O/bench.log"; exit 4; }
 tail -1 "$O/bench.log" | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())
@@ -19,7 +19,7 @@ print('headline', d['value'], d['roofline']['frac'], d['cpu_baseline'] and d['cp
 for k,v in d['aux'].items(): print(f\"{k:24s} {v.get('kernel_ms',0):8.4f} ms  frac {v.get('hbm_frac',0):.3f}\")
 "
 if [ "${KT:-1}" = 1 ]; then
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/bench_kt" -o kt -- python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$O/bench_kt.log" 2>&1 || { echo "bench kt failed"; tail -20 "$O/bench_kt.log"; exit 5; }
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/bench_kt" -o kt -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > "$O/bench_kt.log" 2>&1 || { echo "bench kt failed"; tail -20 "$O/bench_kt.log"; exit 5; }
 fi
 if [ -n "${WLS:-}" ]; then
   WLS="$WLS" bash scripts/gpu_profile_workloads.sh || exit 6

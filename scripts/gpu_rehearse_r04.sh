@@ -10,7 +10,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; cd "$R"; mkdir -p gpurun_out
 G=$((1 << 26))
 for N in ${NS:-4 8}; do
   t0=$(date +%s.%N)
-  QE_DEVICE_MOD=1 QE_DIST_BACKEND=gloo timeout -k 10 500 python bench.py --gpus $N --groups $((G / N)) \
+  QE_DEVICE_MOD=1 QE_DIST_BACKEND=gloo timeout -k 10 500 python bench.py --full --gpus $N --groups $((G / N)) \
     --aux-groups-div $N --no-cpu-baseline > gpurun_out/reh_aux_$N.log 2>&1 \
     || { echo "$N-rank run failed"; tail -30 gpurun_out/reh_aux_$N.log; exit 3; }
   t1=$(date +%s.%N)

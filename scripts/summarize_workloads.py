@@ -23,8 +23,9 @@ read traffic is 2 x FETCH_SIZE.  WRITE_SIZE counts whole 32-B sectors: exact for
 write traffic as is.  (Rounds 1-3 used x1 for the narrow-access kernels,
 which undercounted their reads by half; check_quorum's figure fell below
 its algorithmic bytes.)  usage: summarize_workloads.py <tag> [dir] [bench.log ...]:
-with a bench JSON line, every workload's traffic is checked against its
-algorithmic bytes (units x bytes_per_unit) and a figure below it is refused.
+with a bench JSON line (of a `bench.py --full` run, which holds every aux
+workload), every workload's traffic is checked against its algorithmic bytes
+(units x bytes_per_unit) and a figure below it is refused.
 """
 import csv
 import glob
