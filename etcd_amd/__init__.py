@@ -13,5 +13,6 @@ from .quorum import (INF, AckedIndexer, CommittedIndexBatch, Index, JointConfig,
 from .tracker import (CommittedBatch, MakeProgressTracker, Progress,  # noqa: F401
                       ProgressTracker, QuorumActiveBatch, TallyVotesBatch)
 from . import confchange  # noqa: F401  (raft/confchange mirror)
+from .engine import Timers, tick  # noqa: F401  (raft.tick() over the resident timers)
 
 __version__ = "0.1.0"

@@ -139,6 +139,22 @@ class QeLeader(C.Structure):  # ABI 7
                 ("sent", vp), ("snap", vp)]
 
 
+class QeTimers(C.Structure):  # qe_tick
+    _fields_ = [("state", vp), ("timer", vp), ("randomized_timeout", vp), ("no_campaign", vp),
+                ("events", vp), ("election_timeout", u32), ("heartbeat_timeout", u32),
+                ("flags", u32), ("ticks", u32), ("seed", u64), ("tick_no", u64)]
+
+
+class QeTickOut(C.Structure):  # qe_tick
+    _fields_ = [("action", vp), ("hb_commit", vp), ("hb_ctx", vp), ("hb_sent", vp),
+                ("quorum_active", vp)]
+
+
+QE_TICK_CHECK_QUORUM = 1
+QE_TEV_HEARD, QE_TEV_RESET = 1, 2
+QE_TICK_HUP, QE_TICK_BEAT, QE_TICK_CHECKED_QUORUM, QE_TICK_STEPDOWN = 1, 2, 4, 8
+QE_TICK_TRANSFER_ABORTED = 16
+
 QE_BL_NONE, QE_BL_LEADER, QE_BL_NOT_MEMBER, QE_BL_RUNS_FULL = 0, 1, 2, 3
 QE_BL_BCAST = 1
 
@@ -232,6 +248,8 @@ PROTOTYPES = {
     "qe_read_index": (C.c_int, [C.POINTER(QeProgress), vp, vp, u32, vp, vp, vp, vp]),
     "qe_propose": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeProposals), vp, vp]),
     "qe_heartbeat": (C.c_int, [C.POINTER(QeProgress), vp, vp, vp, vp]),
+    "qe_tick": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeTimers), C.POINTER(QeTickOut), vp,
+                          vp]),
     "qe_switch_config": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeSwitch), vp, vp]),
     "qe_become_leader": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeLeader), vp, vp]),
     "qe_ring_pack": (C.c_int, [u64, u32, u32, u64, vp, vp, vp, vp]),

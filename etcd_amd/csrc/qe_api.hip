@@ -6,6 +6,7 @@
 #include "qe_dispatch.hpp"
 #include "qe_conf.hpp"
 #include "qe_collect.hpp"
+#include "qe_tick.hpp"
 
 namespace qe {
 
@@ -102,6 +103,12 @@ static int dispatch_elec(uint32_t S, const EArgs &a, hipStream_t st) {
 static int dispatch_progress(uint32_t S, const PArgs &a, int kind, bool masked, bool joint,
                              hipStream_t st) {
 #define QE_C(n) dispatch_progress_##n(a, kind, masked, joint, st)
+  QE_SWITCH(S, QE_C)
+#undef QE_C
+}
+
+static int dispatch_tick(uint32_t S, const TArgs &a, bool masked, bool joint, hipStream_t st) {
+#define QE_C(n) dispatch_tick_##n(a, masked, joint, st)
   QE_SWITCH(S, QE_C)
 #undef QE_C
 }
@@ -578,6 +585,66 @@ int qe_heartbeat(const qe_progress *p, uint64_t *commit, uint32_t *ctx, void *se
   a.hb_ctx = ctx;
   a.sent = sent;
   return dispatch_progress(p->num_slots, a, 7, false, false, static_cast<hipStream_t>(stream));
+}
+
+int qe_tick(const qe_progress *p, const qe_timers *t, const qe_tick_out *out, uint64_t *stats,
+            void *stream) {
+  if (!p || !t || !out) return QE_EINVAL;
+  if (p->num_slots == 0 || p->num_slots > QE_MAX_SLOTS || p->reserved || p->reserved2)
+    return QE_EINVAL;
+  if (p->num_groups == 0) return QE_OK;
+  if (!t->state || !t->timer || !t->randomized_timeout || !out->action) return QE_EINVAL;
+  // 2 * election_timeout - 1 must fit the saturating 16-bit counters
+  if (t->election_timeout == 0 || t->election_timeout > 32768u) return QE_EINVAL;
+  if (t->heartbeat_timeout == 0 || t->heartbeat_timeout > 65535u) return QE_EINVAL;
+  if ((t->flags & ~QE_TICK_CHECK_QUORUM) || t->ticks > 1) return QE_EINVAL;
+  if (p->out_mask && !p->inc_mask) return QE_EINVAL;
+  const bool checks = (t->flags & QE_TICK_CHECK_QUORUM) && t->ticks == 1;
+  if (checks && !p->peer) return QE_EINVAL;
+  // the [S][stride] rows it touches: the peer words, Match and hb_commit
+  if ((checks || out->hb_commit) && p->stride < p->num_groups) return QE_EINVAL;
+  if (out->hb_commit && (!p->match || !p->committed)) return QE_EINVAL;
+  if (p->read_acks && (!p->read_head || !p->read_count)) return QE_EINVAL;
+  TArgs a{};
+  {
+    PArgs q{};  // (the queue's capacity rules are qe_heartbeat's)
+    const int rq = read_queue_args(p, q);
+    if (rq) return rq;
+    a.read_cap = q.read_cap;
+  }
+  a.G = p->num_groups;
+  a.goff = p->group_offset;
+  a.stride = p->stride;
+  a.state = t->state;
+  a.timer = t->timer;
+  a.rt = t->randomized_timeout;
+  a.no_campaign = t->no_campaign;
+  a.events = t->events;
+  a.et = t->election_timeout;
+  a.ht = t->heartbeat_timeout;
+  a.flags = t->flags;
+  a.ticks = t->ticks;
+  a.seed = t->seed;
+  a.tick_no = static_cast<uint32_t>(t->tick_no);
+  a.pw = p->peer;
+  a.match = p->match;
+  a.committed = p->committed;
+  a.inc = p->inc_mask;
+  a.out = p->out_mask;
+  a.tracked = p->tracked;
+  a.self_slot = p->self_slot;
+  a.transferee = p->lead_transferee;
+  a.read_acks = p->read_acks;
+  a.read_head = p->read_head;
+  a.read_count = p->read_count;
+  a.action = out->action;
+  a.hb_commit = out->hb_commit;
+  a.hb_ctx = out->hb_ctx;
+  a.hb_sent = out->hb_sent;
+  a.qactive = out->quorum_active;
+  a.stats = stats;
+  return dispatch_tick(p->num_slots, a, p->inc_mask != nullptr, p->out_mask != nullptr,
+                       static_cast<hipStream_t>(stream));
 }
 
 int qe_read_index(const qe_progress *p, const uint8_t *request, const uint64_t *key,

@@ -1,0 +1,34 @@
+// qe_inst_tick.hip — per-slot-count instantiations of the tick kernel
+// (qe_tick.hpp).  Compiled once per S (1..16) with -DQE_S=<S>, in objects of
+// its own: the Progress kernels' objects (qe_inst_prog.hip) do not see it.
+#include "qe_tick.hpp"
+
+#ifndef QE_S
+#error "compile with -DQE_S=<slots>"
+#endif
+
+namespace qe {
+
+namespace {
+constexpr int S = QE_S;
+using MT = std::conditional<(S <= 8), uint8_t, uint16_t>::type;
+}  // namespace
+
+#define QE_CAT2(a, b) a##b
+#define QE_CAT(a, b) QE_CAT2(a, b)
+
+// One tile per wave (as qe_heartbeat).  With statistics the grid is capped
+// and the waves walk: every wave ends with one atomic per counter.
+int QE_CAT(dispatch_tick_, QE_S)(const TArgs &a, bool masked, bool joint, hipStream_t st) {
+  const uint64_t tiles = (a.G + 63) / 64;
+  uint64_t blocks = (tiles + (kBlock / 64) - 1) / (kBlock / 64);
+  const uint64_t cap = a.stats ? static_cast<uint64_t>(num_cus()) * 8 : 0x7FFFFFFFull;
+  if (blocks > cap) blocks = cap;
+  const dim3 grid(static_cast<unsigned>(blocks ? blocks : 1));
+  if (joint) hipLaunchKernelGGL((k_tick<S, MT, true, true>), grid, dim3(kBlock), 0, st, a);
+  else if (masked) hipLaunchKernelGGL((k_tick<S, MT, true, false>), grid, dim3(kBlock), 0, st, a);
+  else hipLaunchKernelGGL((k_tick<S, MT, false, false>), grid, dim3(kBlock), 0, st, a);
+  return hip_status(hipGetLastError());
+}
+
+}  // namespace qe

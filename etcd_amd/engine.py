@@ -671,6 +671,119 @@ def heartbeat(ps, commit=None, ctx=None, sent=None):
     return commit, ctx, sent
 
 
+class Timers:
+    """Device-resident tick state of G groups (qe_timers): `state` u8
+    QE_STATE_*, `timer` int32 storage of electionElapsed | heartbeatElapsed
+    << 16, `randomized_timeout` int16 storage of the u16
+    randomizedElectionTimeout, `no_campaign` u8 (hasPendingSnapshot),
+    `events` u8 QE_TEV_* (cleared by the tick() that consumes them).
+    check_quorum is raft.Config.CheckQuorum; `tick_no` counts the ticks run
+    and is the counter of the timeout draw."""
+
+    def __init__(self, G, election_timeout=10, heartbeat_timeout=1, check_quorum=False,
+                 seed=0, device="cuda", tick_no=0):
+        if not 1 <= int(election_timeout) <= 32768 or not 1 <= int(heartbeat_timeout) <= 65535:
+            raise ValueError("election_timeout must be 1..32768, heartbeat_timeout 1..65535")
+        self.G = int(G)
+        self.device = torch.device(device)
+        self.election_timeout, self.heartbeat_timeout = int(election_timeout), int(heartbeat_timeout)
+        self.check_quorum = bool(check_quorum)
+        self.seed, self.tick_no = int(seed), int(tick_no)
+        dev = self.device
+        self.state = torch.zeros(self.G, dtype=torch.uint8, device=dev)
+        self.timer = torch.zeros(self.G, dtype=torch.int32, device=dev)
+        et = self.election_timeout
+        self.randomized_timeout = torch.full((self.G,), et if et < 32768 else et - 65536,
+                                             dtype=torch.int16, device=dev)
+        self.no_campaign = torch.zeros(self.G, dtype=torch.uint8, device=dev)
+        self.events = torch.zeros(self.G, dtype=torch.uint8, device=dev)
+
+    ARRAYS = ("state", "timer", "randomized_timeout", "no_campaign", "events")
+
+    def load_host(self, **arrays):
+        """numpy arrays: state / no_campaign / events uint8, timer uint32,
+        randomized_timeout uint16; election_elapsed / heartbeat_elapsed (any
+        integers, clipped to the counters' 65535) are packed into timer."""
+        if "election_elapsed" in arrays or "heartbeat_elapsed" in arrays:
+            ee = np.minimum(np.asarray(arrays.pop("election_elapsed", 0), np.int64), 0xFFFF)
+            he = np.minimum(np.asarray(arrays.pop("heartbeat_elapsed", 0), np.int64), 0xFFFF)
+            arrays["timer"] = np.broadcast_to(ee | (he << 16), (self.G,)).astype(np.uint32)
+        for k, a in arrays.items():
+            if k not in self.ARRAYS:
+                raise KeyError(k)
+            a = np.ascontiguousarray(a)
+            if a.dtype == np.uint32:
+                a = a.view(np.int32)
+            elif a.dtype == np.uint16:
+                a = a.view(np.int16)
+            getattr(self, k).copy_(torch.from_numpy(a.copy()).to(self.device))
+        return self
+
+    def reset(self, mask):
+        """The timer part of raft.reset() (becomeFollower / Candidate /
+        Leader) on the groups of `mask` (bool tensor [G]): applied by the
+        next tick() as QE_TEV_RESET."""
+        self.events[mask.to(self.device)] |= _lib.QE_TEV_RESET
+        return self
+
+    def heard(self, mask):
+        """electionElapsed = 0 on the groups of `mask` (QE_TEV_HEARD)."""
+        self.events[mask.to(self.device)] |= _lib.QE_TEV_HEARD
+        return self
+
+    def struct(self, events=None, ticks=1):
+        return _lib.QeTimers(_ptr(self.state), _ptr(self.timer), _ptr(self.randomized_timeout),
+                             _ptr(self.no_campaign), _ptr(events), self.election_timeout,
+                             self.heartbeat_timeout,
+                             _lib.QE_TICK_CHECK_QUORUM if self.check_quorum else 0, int(ticks),
+                             self.seed, self.tick_no)
+
+    def host(self):
+        out = {k: getattr(self, k).cpu().numpy() for k in self.ARRAYS}
+        out["timer"] = out["timer"].view(np.uint32)
+        out["randomized_timeout"] = out["randomized_timeout"].view(np.uint16)
+        return out
+
+
+class TickOut:
+    """Outputs of qe_tick (qe_tick_out): `action` u8 QE_TICK_*, and where a
+    group beat / was checked: hb_commit int64 [S][stride], hb_ctx int32 [G],
+    hb_sent mask [G], quorum_active u8 [G]."""
+
+    def __init__(self, ps, beats=True):
+        dev = ps.device
+        self.action = torch.zeros(ps.G, dtype=torch.uint8, device=dev)
+        self.hb_commit = (torch.zeros(ps.S * ps.stride, dtype=torch.int64, device=dev)
+                          if beats else None)
+        self.hb_ctx = torch.zeros(ps.G, dtype=torch.int32, device=dev) if beats else None
+        self.hb_sent = torch.zeros(ps.G, dtype=mask_torch_dtype(ps.S), device=dev)
+        self.quorum_active = torch.zeros(ps.G, dtype=torch.uint8, device=dev)
+
+    def struct(self):
+        return _lib.QeTickOut(_ptr(self.action), _ptr(self.hb_commit), _ptr(self.hb_ctx),
+                              _ptr(self.hb_sent), _ptr(self.quorum_active))
+
+
+def tick(ps, timers, out=None, stats=None, events=None, ticks=1):
+    """qe_tick: raft.tick() on every group -- tickElection / tickHeartbeat
+    (raft/raft.go:645-684) over the resident timers, with the MsgCheckQuorum
+    and MsgBeat they fire run in the same pass -> TickOut.  events (uint8[G]
+    QE_TEV_*) default to timers.events, which are consumed (cleared) by the
+    call; ticks=0 applies the events alone."""
+    if out is None:
+        out = TickOut(ps)
+    own = events is None
+    if own:
+        events = timers.events
+    p, t, o = ps.struct(), timers.struct(events, ticks), out.struct()
+    check("qe_tick", _lib.lib().qe_tick(C.byref(p), C.byref(t), C.byref(o), _ptr(stats),
+                                         _stream(ps.device)))
+    if own:
+        timers.events.zero_()
+    timers.tick_no += int(ticks)
+    return out
+
+
 class Proposals:
     """One MsgProp per group for qe_propose (qe_proposals, ABI 6):
     num_entries [G] (0 = none), payload [G] (sum of the non-conf-change

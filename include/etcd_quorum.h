@@ -523,7 +523,8 @@ typedef struct qe_peer_msgs {
  *     otherwise lead_transferee = the slot, and MsgTimeoutNow goes out at
  *     once when its Match == lastIndex, else sendAppend to it.  (The
  *     reference also resets electionElapsed: tick state stays with the host,
- *     which sees the new lead_transferee.)
+ *     which sees the new lead_transferee and reports it to the next tick as
+ *     QE_TEV_HEARD.)
  * A send is raft.maybeSendAppend (raft.go:432-492) on the log model; see
  * qe_progress_send.  Messages from untracked slots are dropped.  An accept
  * with index > lastIndex is processed as the reference does and counted as
@@ -603,6 +604,112 @@ int qe_check_quorum(const qe_progress *p, uint8_t *quorum_active, uint64_t *stat
  * match, committed, tracked, self_slot and the ReadIndex queue's head and
  * count; writes nothing of p. */
 int qe_heartbeat(const qe_progress *p, uint64_t *commit, uint32_t *ctx, void *sent, void *stream);
+
+/* raft.tick() on every group (additive; the ABI version does not change):
+ * tickElection (raft/raft.go:645-654) where state[g] != QE_STATE_LEADER,
+ * tickHeartbeat (:657-684) where it leads -- the per-group gate in front of
+ * MsgHup, MsgCheckQuorum and MsgBeat, with the latter two executed in the same
+ * pass exactly as qe_check_quorum / qe_heartbeat execute them on that group.
+ *
+ * The timers: electionElapsed and heartbeatElapsed are 16-bit counters that
+ * saturate at 65535.  A saturating 16-bit counter compares against any
+ * threshold <= 65535 exactly as the reference's int does, and the largest
+ * threshold is randomizedElectionTimeout <= 2*election_timeout - 1: hence
+ * election_timeout <= 32768, the only bound.
+ *
+ * Per group, in this order:
+ *  1. events[g] (what happened since the last tick): QE_TEV_HEARD ->
+ *     electionElapsed = 0; QE_TEV_RESET -> both counters 0 and
+ *     randomizedElectionTimeout drawn again (RESET wins over HEARD).  With
+ *     ticks == 0 the call ends here for the group, action[g] = 0.
+ *  2. state != leader (tickElection): electionElapsed++; if promotable()
+ *     (:1618-1621) and pastElectionTimeout() (:1711-1713: electionElapsed >=
+ *     randomizedElectionTimeout): electionElapsed = 0, QE_TICK_HUP.  The
+ *     campaign (its pending-conf-change check, becomeCandidate's reset())
+ *     stays with the caller -- qe_election_steps' script_hup or the host --
+ *     which reports the reset() back as QE_TEV_RESET.  promotable: self_slot[g]
+ *     < S, that slot in `tracked` (NULL = every slot) and in inc_mask |
+ *     out_mask (NULL inc_mask = every slot a voter; LearnersNext sit in
+ *     out_mask and count), and no_campaign[g] == 0; NULL self_slot = nobody.
+ *  3. state == leader (tickHeartbeat): both counters++.  electionElapsed >=
+ *     election_timeout -> electionElapsed = 0 and
+ *       with QE_TICK_CHECK_QUORUM, MsgCheckQuorum (:997-1018, see
+ *       qe_check_quorum): QE_TICK_CHECKED_QUORUM, quorum_active[g] written;
+ *       not active -> becomeFollower(r.Term, None): state = follower, both
+ *       counters 0, the timeout drawn again, lead_transferee = none,
+ *       QE_TICK_STEPDOWN.  The peer words are left as qe_check_quorum leaves
+ *       them: the wholesale Progress reset of reset() (:600-616) is
+ *       qe_become_leader's, the next time the group leads;
+ *       still leader with lead_transferee[g] < S -> abortLeaderTransfer
+ *       (:669-671).  QE_TICK_TRANSFER_ABORTED whenever the stored transferee
+ *       went from a slot to none, by either path.
+ *     No longer leader: nothing more (no beat on a stepdown tick).
+ *     heartbeatElapsed >= heartbeat_timeout -> heartbeatElapsed = 0, MsgBeat:
+ *     QE_TICK_BEAT and the outputs of qe_heartbeat for the group (hb_commit
+ *     rows of the slots sent to, hb_ctx, hb_sent).
+ *  4. a draw is election_timeout + ((hash4(seed, group_offset + g,
+ *     (uint32_t)tick_no, 0x7131) >> 32) * election_timeout >> 32), hash4(seed,
+ *     gid, lane, stream) = mix64(mix64(seed + gid * 0x9E3779B97F4A7C15) ^
+ *     ((stream << 32 | lane) * 0xD6E8FEB86659FD93)), mix64 the splitmix64
+ *     finalizer: uniform over [election_timeout, 2*election_timeout - 1] as
+ *     the reference's globalRand.Intn (:1718-1720), a function of the global
+ *     group id and the tick number alone (shards and replays agree).
+ * Reads of p: inc_mask / out_mask / tracked / self_slot, peer (CheckQuorum),
+ * match / committed and the ReadIndex queue's head and count (beats); writes
+ * peer words and lead_transferee.  hb_sent[g] = 0 and nothing else of hb_* is
+ * written where there is no beat; quorum_active only where the check ran.
+ * stats: QE_STAT_GROUPS, QE_STAT_ELECTIONS (HUPs), QE_STAT_STEPDOWNS,
+ * QE_STAT_CHECKSUM += mix64((group_offset + g) * 0x9E3779B97F4A7C15 ^
+ * 0xA0761D6478BD642F ^ action << 56 ^ randomized_timeout << 32 ^ timer), the
+ * values after the tick.
+ * QE_EINVAL: a NULL p / t / out / state / timer / randomized_timeout /
+ * action, a timeout out of range, unknown flag bits, ticks > 1, out_mask
+ * without inc_mask, QE_TICK_CHECK_QUORUM with ticks == 1 and no p->peer,
+ * hb_commit without p->match / p->committed or with stride < num_groups,
+ * read_acks without read_head / read_count.  num_groups == 0 is QE_OK. */
+#define QE_TICK_CHECK_QUORUM 1u      /* qe_timers.flags: raft.Config.CheckQuorum */
+
+/* events[g], applied before the tick */
+#define QE_TEV_HEARD 1u   /* electionElapsed = 0: a follower got MsgApp/MsgHeartbeat/
+                             MsgSnap from its leader (raft.go:1434-1442), granted a
+                             vote (:971), or the leader accepted MsgTransferLeader (:1362) */
+#define QE_TEV_RESET 2u   /* the timer part of raft.reset() (:597-599): both elapsed
+                             counters 0, randomizedElectionTimeout drawn again
+                             (becomeFollower/Candidate/Leader) */
+
+/* action[g] */
+#define QE_TICK_HUP 1u              /* tickElection fired: the host steps MsgHup      */
+#define QE_TICK_BEAT 2u             /* MsgBeat ran: hb_* outputs are valid for g      */
+#define QE_TICK_CHECKED_QUORUM 4u   /* MsgCheckQuorum ran on g                        */
+#define QE_TICK_STEPDOWN 8u         /* ... and QuorumActive was false                 */
+#define QE_TICK_TRANSFER_ABORTED 16u/* lead_transferee went from a slot to none       */
+
+typedef struct qe_timers {
+  uint8_t  *state;              /* [G] rw QE_STATE_*; the tick writes it only on a stepdown */
+  uint32_t *timer;              /* [G] rw: electionElapsed bits 0-15, heartbeatElapsed
+                                   bits 16-31, each saturating at 65535 */
+  uint16_t *randomized_timeout; /* [G] rw r.randomizedElectionTimeout */
+  const uint8_t *no_campaign;   /* [G] or NULL: raftLog.hasPendingSnapshot() */
+  const uint8_t *events;        /* [G] or NULL: QE_TEV_* */
+  uint32_t election_timeout;    /* Config.ElectionTick, 1..32768 */
+  uint32_t heartbeat_timeout;   /* Config.HeartbeatTick, 1..65535 */
+  uint32_t flags;               /* QE_TICK_CHECK_QUORUM; other bits -> QE_EINVAL */
+  uint32_t ticks;               /* 1 = one tick; 0 = apply events only */
+  uint64_t seed;                /* of the timeout draw */
+  uint64_t tick_no;             /* the host's tick counter, the draw's counter */
+} qe_timers;
+
+typedef struct qe_tick_out {
+  uint8_t  *action;      /* [G] QE_TICK_* (required) */
+  uint64_t *hb_commit;   /* [S][stride], as the commit of the MsgBeat entry point; NULL =
+                            beats reported in action only */
+  uint32_t *hb_ctx;      /* [G] or NULL */
+  void     *hb_sent;     /* [G] mask-typed or NULL; 0 where no beat */
+  uint8_t  *quorum_active; /* [G] or NULL; written only where CHECKED_QUORUM */
+} qe_tick_out;
+
+int qe_tick(const qe_progress *p, const qe_timers *t, const qe_tick_out *out,
+            uint64_t *stats, void *stream);
 
 /* raft.sendAppend / maybeSendAppend(to, send_if_empty) once for the slots of
  * want[g] (raft.go:432-492; bcastAppend after a proposal is want = every
