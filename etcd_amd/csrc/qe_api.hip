@@ -70,49 +70,6 @@ __global__ void k_stats_reduce(const uint64_t *stats, uint64_t *out) {
 }
 
 
-#define QE_SWITCH(S, CALL)                                                              \
-  switch (S) {                                                                          \
-    case 1: return CALL(1); case 2: return CALL(2); case 3: return CALL(3);             \
-    case 4: return CALL(4); case 5: return CALL(5); case 6: return CALL(6);             \
-    case 7: return CALL(7); case 8: return CALL(8); case 9: return CALL(9);             \
-    case 10: return CALL(10); case 11: return CALL(11); case 12: return CALL(12);       \
-    case 13: return CALL(13); case 14: return CALL(14); case 15: return CALL(15);       \
-    case 16: return CALL(16);                                                           \
-    default: return QE_EINVAL;                                                          \
-  }
-
-static int dispatch_cv(uint32_t S, const CVArgs &a, int mode, bool vec, hipStream_t st) {
-#define QE_C(n) dispatch_cv_##n(a, mode, vec, st)
-  QE_SWITCH(S, QE_C)
-#undef QE_C
-}
-
-static int dispatch_repl(uint32_t S, const RArgs &a, bool masked, bool joint, bool vec,
-                         hipStream_t st) {
-#define QE_C(n) dispatch_repl_##n(a, masked, joint, vec, st)
-  QE_SWITCH(S, QE_C)
-#undef QE_C
-}
-
-static int dispatch_elec(uint32_t S, const EArgs &a, hipStream_t st) {
-#define QE_C(n) dispatch_elec_##n(a, st)
-  QE_SWITCH(S, QE_C)
-#undef QE_C
-}
-
-static int dispatch_progress(uint32_t S, const PArgs &a, int kind, bool masked, bool joint,
-                             hipStream_t st) {
-#define QE_C(n) dispatch_progress_##n(a, kind, masked, joint, st)
-  QE_SWITCH(S, QE_C)
-#undef QE_C
-}
-
-static int dispatch_tick(uint32_t S, const TArgs &a, bool masked, bool joint, hipStream_t st) {
-#define QE_C(n) dispatch_tick_##n(a, masked, joint, st)
-  QE_SWITCH(S, QE_C)
-#undef QE_C
-}
-
 }  // namespace qe
 
 // ===========================================================================
@@ -213,7 +170,9 @@ int qe_commit_vote(const qe_groups *g, const qe_outputs *out, void *stream) {
   for (const void *m : masks) vec = vec && al(m, 2 * mb);
   const uint8_t *bytes[] = {out->vote, out->granted_count, out->rejected_count};
   for (const uint8_t *b : bytes) vec = vec && al(b, 2);
-  return dispatch_cv(g->num_slots, a, mode, vec, static_cast<hipStream_t>(stream));
+  return with_slots(g->num_slots, [&](auto s) {
+    return dispatch_cv<s()>(a, mode, vec, static_cast<hipStream_t>(stream));
+  });
 }
 
 int qe_committed_index(const qe_groups *g, uint64_t *commit, void *stream) {
@@ -316,8 +275,10 @@ int qe_replication_round(const qe_repl_state *s, const qe_repl_msgs *m, uint64_t
   const void *pm[] = {s->inc_mask, s->out_mask, m->resp_mask, m->read_acks};
   for (const void *p : pm) vec = vec && al(p, 2 * mb);
   vec = vec && al(m->read_ok, 2) && al(m->commit_advanced, 2);
-  return dispatch_repl(s->num_slots, a, s->inc_mask != nullptr, s->out_mask != nullptr, vec,
-                       static_cast<hipStream_t>(stream));
+  return with_slots(s->num_slots, [&](auto n) {
+    return dispatch_repl<n()>(a, s->inc_mask != nullptr, s->out_mask != nullptr, vec,
+                              static_cast<hipStream_t>(stream));
+  });
 }
 
 int qe_election_steps(const qe_election_state *s, const qe_election_params *p, uint64_t *stats,
@@ -355,7 +316,9 @@ int qe_election_steps(const qe_election_state *s, const qe_election_params *p, u
   a.shup = p->script_resp ? p->script_hup : nullptr;
   a.sstride = p->script_stride;
   a.stats = stats;
-  return dispatch_elec(s->num_slots, a, static_cast<hipStream_t>(stream));
+  return with_slots(s->num_slots, [&](auto n) {
+    return dispatch_elec<n()>(a, static_cast<hipStream_t>(stream));
+  });
 }
 
 int qe_apply_append_resps(uint64_t num_groups, uint32_t num_slots, uint64_t stride,
@@ -371,27 +334,75 @@ int qe_apply_append_resps(uint64_t num_groups, uint32_t num_slots, uint64_t stri
   return hip_status(hipGetLastError());
 }
 
-// The ReadIndex queue's ABI 7 fields: a capacity of 0 is QE_READ_QUEUE (the
-// ABI 5 queue); a longer queue needs the overflow ring.
-static int read_queue_args(const qe_progress *p, PArgs &a) {
-  if (p->reserved3) return QE_EINVAL;
-  if (p->read_cap != 0 && (p->read_cap < QE_READ_QUEUE || p->read_cap > QE_READ_CAP_MAX))
-    return QE_ERANGE;
-  a.read_cap = p->read_cap ? p->read_cap : QE_READ_QUEUE;
-  if (p->read_acks && a.read_cap > QE_READ_QUEUE && !p->read_ovf) return QE_EINVAL;
-  a.read_ovf = p->read_ovf;
-  a.read_keys = p->read_keys;
-  return QE_OK;
-}
-
-static int progress_args(const qe_progress *p, PArgs &a) {
+// The rules every entry point that takes a qe_progress opens with.  (Two
+// gaps ADVICE.md lists are not closed here, being behaviour changes:
+// qe_switch_config accepts a missing self_slot, and qe_read_index accepts
+// read_keys without a key.)
+static int check_progress(const qe_progress *p) {
   if (!p) return QE_EINVAL;
   if (p->num_slots == 0 || p->num_slots > QE_MAX_SLOTS || p->reserved || p->reserved2)
     return QE_EINVAL;
+  return QE_OK;
+}
+
+// the [S][stride] rows hold the batch, and out_mask (a joint configuration)
+// comes with inc_mask
+static bool bad_rows_or_masks(const qe_progress *p) {
+  return (p->num_groups && p->stride < p->num_groups) || (p->out_mask && !p->inc_mask);
+}
+
+// ABI 5: the ReadIndex queue comes whole or not at all
+static bool partial_read_queue(const qe_progress *p) {
+  return p->read_acks && (!p->read_head || !p->read_count);
+}
+
+// The ReadIndex queue's ABI 7 fields: a capacity of 0 is QE_READ_QUEUE (the
+// ABI 5 queue); a longer queue needs the overflow ring.
+static int read_queue_cap(const qe_progress *p, uint32_t *cap) {
+  if (p->reserved3) return QE_EINVAL;
+  if (p->read_cap != 0 && (p->read_cap < QE_READ_QUEUE || p->read_cap > QE_READ_CAP_MAX))
+    return QE_ERANGE;
+  *cap = p->read_cap ? p->read_cap : QE_READ_QUEUE;
+  if (p->read_acks && *cap > QE_READ_QUEUE && !p->read_ovf) return QE_EINVAL;
+  return QE_OK;
+}
+
+// The fields of the state more than one kernel reads.  The partial entry
+// points validate only part of the struct and still get every field here, so
+// their kernels must read only what their entry point checked.  Audited when
+// this was introduced: k_heartbeat reads G, stride, match, committed, tracked,
+// self_slot and the read_* queue; k_check_quorum reads G, goff, stride, pw,
+// inc, out, tracked and self_slot; k_read_index reads G, stride, committed,
+// term_start, last_index, inc, out, self_slot and the read_* queue (with
+// read_ovf and read_keys).  A kernel edit that reads another field here
+// (a.tracked in k_read_index, say) needs the matching check in its entry
+// point first.
+static void state_args(const qe_progress *p, PArgs &a) {
+  a.G = p->num_groups;
+  a.goff = p->group_offset;
+  a.stride = p->stride;
+  a.match = p->match;
+  a.pw = p->peer;
+  a.committed = p->committed;
+  a.term_start = p->term_start;
+  a.last_index = p->last_index;
+  a.inc = p->inc_mask;
+  a.out = p->out_mask;
+  a.tracked = p->tracked;
+  a.self_slot = p->self_slot;
+  a.read_acks = p->read_acks;
+  a.read_head = p->read_head;
+  a.read_count = p->read_count;
+  a.read_ovf = p->read_ovf;
+  a.read_keys = p->read_keys;
+}
+
+static int progress_args(const qe_progress *p, PArgs &a) {
+  const int rc = check_progress(p);
+  if (rc) return rc;
   if (p->inflight_cap == 0 || p->inflight_cap > QE_MAX_INFLIGHT) return QE_ERANGE;
   if (p->log_runs > QE_MAX_LOG_RUNS) return QE_ERANGE;
-  if (p->num_groups && p->stride < p->num_groups) return QE_EINVAL;
-  if (p->out_mask && !p->inc_mask) return QE_EINVAL;
+  if (bad_rows_or_masks(p)) return QE_EINVAL;
   if (p->num_groups &&
       (!p->match || !p->next || !p->pending_snapshot || !p->peer || !p->infl_lo || !p->infl_hi ||
        !p->committed || !p->term_start || !p->first_index || !p->last_index))
@@ -406,37 +417,32 @@ static int progress_args(const qe_progress *p, PArgs &a) {
                     p->log_runs > 4))
     return QE_ERANGE;
   a = PArgs{};
-  a.G = p->num_groups;
-  a.goff = p->group_offset;
-  a.stride = p->stride;
+  state_args(p, a);
   a.F = p->inflight_cap;
   a.R = p->log_runs;
-  a.match = p->match;
   a.next = p->next;
   a.pending = p->pending_snapshot;
-  a.pw = p->peer;
   a.ilo = p->infl_lo;
   a.ihi = p->infl_hi;
   a.infl16 = p->infl16;
   a.FP = QE_RING_PITCH(p->inflight_cap);
-  a.committed = p->committed;
-  a.term_start = p->term_start;
   a.first_index = p->first_index;
-  a.last_index = p->last_index;
   a.snap_index = p->snap_index;
   a.run_first = p->run_first;
   a.run_term = p->run_term;
   a.run_count = p->run_count;
-  a.inc = p->inc_mask;
-  a.out = p->out_mask;
-  a.tracked = p->tracked;
-  a.self_slot = p->self_slot;
   a.transferee = p->lead_transferee;
   a.max_ents = p->max_ents;
-  a.read_acks = p->read_acks;
-  a.read_head = p->read_head;
-  a.read_count = p->read_count;
-  return read_queue_args(p, a);
+  return read_queue_cap(p, &a.read_cap);
+}
+
+// the launch every Progress entry point ends with
+static int launch_progress(const qe_progress *p, const PArgs &a, ProgressOp op, bool acct,
+                           void *stream) {
+  return with_slots(p->num_slots, [&](auto s) {
+    return dispatch_progress<s()>(a, op, acct, p->inc_mask != nullptr, p->out_mask != nullptr,
+                                  static_cast<hipStream_t>(stream));
+  });
 }
 
 int qe_progress_step(const qe_progress *p, const qe_peer_msgs *m, uint64_t *stats,
@@ -459,16 +465,13 @@ int qe_progress_step(const qe_progress *p, const qe_peer_msgs *m, uint64_t *stat
   a.msg_count = m->msg_count;
   a.msg_index = m->msg_index;
   a.acct = m->bytes_requested;
-  // ABI 5: the ReadIndex queue comes whole or not at all
-  if (p->read_acks && (!p->read_head || !p->read_count)) return QE_EINVAL;
+  if (partial_read_queue(p)) return QE_EINVAL;
   a.read_ctx = p->read_acks ? m->read_ctx : nullptr;
   a.read_released = m->read_released;
   a.term_commit = m->term_commit;
   a.term_commit_index = m->term_commit_index;
   a.stats = stats;
-  const int kind = m->bytes_requested ? 2 : 0;
-  return dispatch_progress(p->num_slots, a, kind, p->inc_mask != nullptr, p->out_mask != nullptr,
-                           static_cast<hipStream_t>(stream));
+  return launch_progress(p, a, ProgressOp::Step, m->bytes_requested != nullptr, stream);
 }
 
 int qe_progress_send(const qe_progress *p, const void *want, uint32_t send_if_empty,
@@ -482,7 +485,7 @@ int qe_progress_send(const qe_progress *p, const void *want, uint32_t send_if_em
   a.send_if_empty = send_if_empty;
   a.sent = sent;
   a.snap = snap;
-  return dispatch_progress(p->num_slots, a, 1, false, false, static_cast<hipStream_t>(stream));
+  return launch_progress(p, a, ProgressOp::Send, false, stream);
 }
 
 int qe_propose(const qe_progress *p, const qe_proposals *prop, uint64_t *stats, void *stream) {
@@ -520,8 +523,7 @@ int qe_propose(const qe_progress *p, const qe_proposals *prop, uint64_t *stats, 
   a.acct = prop->bytes_requested;
   a.last_index_rw = const_cast<uint64_t *>(p->last_index);
   a.stats = stats;
-  return dispatch_progress(p->num_slots, a, prop->bytes_requested ? 6 : 5, p->inc_mask != nullptr,
-                           p->out_mask != nullptr, static_cast<hipStream_t>(stream));
+  return launch_progress(p, a, ProgressOp::Propose, prop->bytes_requested != nullptr, stream);
 }
 
 int qe_switch_config(const qe_progress *p, const qe_switch *sw, uint64_t *stats, void *stream) {
@@ -537,8 +539,7 @@ int qe_switch_config(const qe_progress *p, const qe_switch *sw, uint64_t *stats,
   a.snap = sw->snap;
   a.acct = sw->bytes_requested;
   a.stats = stats;
-  return dispatch_progress(p->num_slots, a, sw->bytes_requested ? 9 : 8, p->inc_mask != nullptr,
-                           p->out_mask != nullptr, static_cast<hipStream_t>(stream));
+  return launch_progress(p, a, ProgressOp::SwitchConfig, sw->bytes_requested != nullptr, stream);
 }
 
 int qe_become_leader(const qe_progress *p, const qe_leader *l, uint64_t *stats, void *stream) {
@@ -558,40 +559,30 @@ int qe_become_leader(const qe_progress *p, const qe_leader *l, uint64_t *stats, 
   a.sent = l->sent;
   a.snap = l->snap;
   a.stats = stats;
-  return dispatch_progress(p->num_slots, a, 10, p->inc_mask != nullptr, p->out_mask != nullptr,
-                           static_cast<hipStream_t>(stream));
+  return launch_progress(p, a, ProgressOp::BecomeLeader, false, stream);
 }
 
 int qe_heartbeat(const qe_progress *p, uint64_t *commit, uint32_t *ctx, void *sent, void *stream) {
-  if (!p) return QE_EINVAL;
-  if (p->num_slots == 0 || p->num_slots > QE_MAX_SLOTS || p->reserved || p->reserved2)
-    return QE_EINVAL;
+  const int rc = check_progress(p);
+  if (rc) return rc;
   if (p->num_groups == 0) return QE_OK;
   if (p->stride < p->num_groups || !p->match || !p->committed || !commit) return QE_EINVAL;
-  if (p->read_acks && (!p->read_head || !p->read_count)) return QE_EINVAL;
+  if (partial_read_queue(p)) return QE_EINVAL;
   PArgs a{};
-  a.G = p->num_groups;
-  a.stride = p->stride;
-  a.match = p->match;
-  a.committed = p->committed;
-  a.tracked = p->tracked;
-  a.self_slot = p->self_slot;
-  a.read_acks = p->read_acks;
-  a.read_head = p->read_head;
-  a.read_count = p->read_count;
-  const int rq = read_queue_args(p, a);
+  state_args(p, a);
+  const int rq = read_queue_cap(p, &a.read_cap);
   if (rq) return rq;
   a.hb_commit = commit;
   a.hb_ctx = ctx;
   a.sent = sent;
-  return dispatch_progress(p->num_slots, a, 7, false, false, static_cast<hipStream_t>(stream));
+  return launch_progress(p, a, ProgressOp::Heartbeat, false, stream);
 }
 
 int qe_tick(const qe_progress *p, const qe_timers *t, const qe_tick_out *out, uint64_t *stats,
             void *stream) {
-  if (!p || !t || !out) return QE_EINVAL;
-  if (p->num_slots == 0 || p->num_slots > QE_MAX_SLOTS || p->reserved || p->reserved2)
-    return QE_EINVAL;
+  const int rc = check_progress(p);
+  if (rc) return rc;
+  if (!t || !out) return QE_EINVAL;
   if (p->num_groups == 0) return QE_OK;
   if (!t->state || !t->timer || !t->randomized_timeout || !out->action) return QE_EINVAL;
   // 2 * election_timeout - 1 must fit the saturating 16-bit counters
@@ -604,14 +595,10 @@ int qe_tick(const qe_progress *p, const qe_timers *t, const qe_tick_out *out, ui
   // the [S][stride] rows it touches: the peer words, Match and hb_commit
   if ((checks || out->hb_commit) && p->stride < p->num_groups) return QE_EINVAL;
   if (out->hb_commit && (!p->match || !p->committed)) return QE_EINVAL;
-  if (p->read_acks && (!p->read_head || !p->read_count)) return QE_EINVAL;
+  if (partial_read_queue(p)) return QE_EINVAL;
   TArgs a{};
-  {
-    PArgs q{};  // (the queue's capacity rules are qe_heartbeat's)
-    const int rq = read_queue_args(p, q);
-    if (rq) return rq;
-    a.read_cap = q.read_cap;
-  }
+  const int rq = read_queue_cap(p, &a.read_cap);  // (the capacity rules are qe_heartbeat's)
+  if (rq) return rq;
   a.G = p->num_groups;
   a.goff = p->group_offset;
   a.stride = p->stride;
@@ -643,36 +630,25 @@ int qe_tick(const qe_progress *p, const qe_timers *t, const qe_tick_out *out, ui
   a.hb_sent = out->hb_sent;
   a.qactive = out->quorum_active;
   a.stats = stats;
-  return dispatch_tick(p->num_slots, a, p->inc_mask != nullptr, p->out_mask != nullptr,
-                       static_cast<hipStream_t>(stream));
+  return with_slots(p->num_slots, [&](auto s) {
+    return dispatch_tick<s()>(a, p->inc_mask != nullptr, p->out_mask != nullptr,
+                              static_cast<hipStream_t>(stream));
+  });
 }
 
 int qe_read_index(const qe_progress *p, const uint8_t *request, const uint64_t *key,
                   uint32_t lease_based, uint8_t *result, uint32_t *ctx, uint64_t *index,
                   void *stream) {
-  if (!p) return QE_EINVAL;
-  if (p->num_slots == 0 || p->num_slots > QE_MAX_SLOTS || p->reserved || p->reserved2)
-    return QE_EINVAL;
+  const int rc = check_progress(p);
+  if (rc) return rc;
   if (p->num_groups == 0) return QE_OK;
-  if (p->stride < p->num_groups || !request || !result) return QE_EINVAL;
+  if (bad_rows_or_masks(p) || !request || !result) return QE_EINVAL;
   if (!p->committed || !p->term_start || !p->last_index) return QE_EINVAL;
-  if (p->out_mask && !p->inc_mask) return QE_EINVAL;
   // ReadOnlySafe queues: the queue must be there
   if (!lease_based && (!p->read_acks || !p->read_head || !p->read_count)) return QE_EINVAL;
   PArgs a{};
-  a.G = p->num_groups;
-  a.goff = p->group_offset;
-  a.stride = p->stride;
-  a.committed = p->committed;
-  a.term_start = p->term_start;
-  a.last_index = p->last_index;
-  a.inc = p->inc_mask;
-  a.out = p->out_mask;
-  a.self_slot = p->self_slot;
-  a.read_acks = p->read_acks;
-  a.read_head = p->read_head;
-  a.read_count = p->read_count;
-  const int rq = read_queue_args(p, a);
+  state_args(p, a);
+  const int rq = read_queue_cap(p, &a.read_cap);
   if (rq) return rq;
   a.ri_key = p->read_keys ? key : nullptr;  // keys are checked only when the state keeps them
   a.ri_request = request;
@@ -680,31 +656,20 @@ int qe_read_index(const qe_progress *p, const uint8_t *request, const uint64_t *
   a.ri_ctx = ctx;
   a.ri_index = index;
   a.lease_based = lease_based ? 1u : 0u;
-  return dispatch_progress(p->num_slots, a, 4, p->inc_mask != nullptr, p->out_mask != nullptr,
-                           static_cast<hipStream_t>(stream));
+  return launch_progress(p, a, ProgressOp::ReadIndex, false, stream);
 }
 
 int qe_check_quorum(const qe_progress *p, uint8_t *quorum_active, uint64_t *stats,
                     void *stream) {
-  if (!p) return QE_EINVAL;
-  if (p->num_slots == 0 || p->num_slots > QE_MAX_SLOTS || p->reserved || p->reserved2)
-    return QE_EINVAL;
+  const int rc = check_progress(p);
+  if (rc) return rc;
   if (p->num_groups == 0) return QE_OK;
-  if (p->stride < p->num_groups || !p->peer) return QE_EINVAL;
-  if (p->out_mask && !p->inc_mask) return QE_EINVAL;
+  if (bad_rows_or_masks(p) || !p->peer) return QE_EINVAL;
   PArgs a{};
-  a.G = p->num_groups;
-  a.goff = p->group_offset;
-  a.stride = p->stride;
-  a.pw = p->peer;
-  a.inc = p->inc_mask;
-  a.out = p->out_mask;
-  a.tracked = p->tracked;
-  a.self_slot = p->self_slot;
+  state_args(p, a);
   a.qactive = quorum_active;
   a.stats = stats;
-  return dispatch_progress(p->num_slots, a, 3, p->inc_mask != nullptr, p->out_mask != nullptr,
-                           static_cast<hipStream_t>(stream));
+  return launch_progress(p, a, ProgressOp::CheckQuorum, false, stream);
 }
 
 int qe_confchange(const qe_conf *c, const qe_conf_changes *ch, const qe_progress *p,
@@ -749,29 +714,17 @@ int qe_confchange(const qe_conf *c, const qe_conf_changes *ch, const qe_progress
     a.p_pending = p->pending_snapshot;
     a.p_pw = p->peer;
   }
-  // chunks of up to kCCTPW tiles per wave, >= 2 so the two register sets
-  // overlap; shorter chunks when the batch cannot give every CU 32 waves
-  const uint64_t tiles = (a.G + 63) / 64;
-  const uint64_t waves = static_cast<uint64_t>(num_cus()) * 32;
-  uint64_t chunk = g_tiles_per_wave > 0 ? static_cast<uint64_t>(g_tiles_per_wave)
-                                        : (tiles + waves - 1) / waves;
-  if (chunk < 2) chunk = 2;
-  if (chunk > static_cast<uint64_t>(kCCTPW)) chunk = kCCTPW;
-  a.chunk = static_cast<uint32_t>(chunk);
-  const uint64_t per_block = (kBlock / 64) * chunk;
-  const uint64_t blocks = (tiles + per_block - 1) / per_block;
-  if (blocks > 0x7FFFFFFFull) return QE_ERANGE;
-  const dim3 grid(static_cast<unsigned>(blocks));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  switch (c->num_slots) {
-#define QE_CC_CASE(n) \
-  case n: hipLaunchKernelGGL(k_confchange<n>, grid, dim3(kBlock), 0, st, a); break;
-    QE_CC_CASE(1) QE_CC_CASE(2) QE_CC_CASE(3) QE_CC_CASE(4) QE_CC_CASE(5) QE_CC_CASE(6)
-    QE_CC_CASE(7) QE_CC_CASE(8) QE_CC_CASE(9) QE_CC_CASE(10) QE_CC_CASE(11) QE_CC_CASE(12)
-    QE_CC_CASE(13) QE_CC_CASE(14) QE_CC_CASE(15) QE_CC_CASE(16)
-#undef QE_CC_CASE
-  }
-  return hip_status(hipGetLastError());
+  // chunks of up to kCCTPW tiles per wave (the chunk plan of qe_launch.hpp;
+  // a tiles_per_wave override is floored at 2 too)
+  const ChunkPlan plan =
+      chunk_plan((a.G + 63) / 64, num_cus(), g_tiles_per_wave, kCCTPW, true);
+  if (plan.status) return plan.status;
+  a.chunk = plan.chunk;
+  return with_slots(c->num_slots, [&](auto s) {
+    hipLaunchKernelGGL(k_confchange<s()>, dim3(plan.blocks), dim3(kBlock), 0,
+                       static_cast<hipStream_t>(stream), a);
+    return hip_status(hipGetLastError());
+  });
 }
 
 size_t qe_collect_scratch_bytes(uint64_t num_groups) {

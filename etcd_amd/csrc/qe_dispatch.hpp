@@ -1,5 +1,8 @@
 // qe_dispatch.hpp — declarations shared by the per-S instantiation objects
-// (qe_inst.hip) and the C ABI (qe_api.hip).
+// (qe_inst.hip, qe_inst_prog.hip) and the C ABI (qe_api.hip).  Each
+// dispatch_* is a function template over the slot count, defined in the .hip
+// that holds its kernels and instantiated there for that object's QE_S;
+// qe_api.hip picks the instantiation with with_slots (qe_launch.hpp).
 #pragma once
 #include "qe_kernels.hpp"
 #include "qe_stream.hpp"
@@ -10,16 +13,20 @@ namespace qe {
 
 int hip_status(hipError_t e);
 
-#define QE_DECL_S(n)                                                                   \
-  int dispatch_cv_##n(const CVArgs &a, int mode, bool vec, hipStream_t st);           \
-  int dispatch_repl_##n(const RArgs &a, bool masked, bool joint, bool vec,            \
-                        hipStream_t st);                                               \
-  int dispatch_elec_##n(const EArgs &a, hipStream_t st);                            \
-  int dispatch_progress_##n(const PArgs &a, int kind, bool masked, bool joint,        \
-                            hipStream_t st);
-QE_DECL_S(1) QE_DECL_S(2) QE_DECL_S(3) QE_DECL_S(4) QE_DECL_S(5) QE_DECL_S(6) QE_DECL_S(7)
-QE_DECL_S(8) QE_DECL_S(9) QE_DECL_S(10) QE_DECL_S(11) QE_DECL_S(12) QE_DECL_S(13)
-QE_DECL_S(14) QE_DECL_S(15) QE_DECL_S(16)
-#undef QE_DECL_S
+// the Progress entry points that launch through dispatch_progress
+enum class ProgressOp { Step, Send, CheckQuorum, ReadIndex, Propose, Heartbeat, SwitchConfig,
+                        BecomeLeader };
+
+template <int S>
+int dispatch_cv(const CVArgs &a, int mode, bool vec, hipStream_t st);
+template <int S>
+int dispatch_repl(const RArgs &a, bool masked, bool joint, bool vec, hipStream_t st);
+template <int S>
+int dispatch_elec(const EArgs &a, hipStream_t st);
+// acct: the instrumented variant with byte accounting (Step, Propose and
+// SwitchConfig have one; measurement only)
+template <int S>
+int dispatch_progress(const PArgs &a, ProgressOp op, bool acct, bool masked, bool joint,
+                      hipStream_t st);
 
 }  // namespace qe

@@ -26,28 +26,19 @@ int launch_cv_k(const CVArgs &a, hipStream_t st) {
   return hip_status(hipGetLastError());
 }
 
-// Chunk (tiles per wave): QE_STREAM_TPW on large batches; a batch too small
-// to give every CU 32 waves at that chunk gets shorter chunks (>= 2, so the
-// two-set pipeline still overlaps), trading per-wave pipelining for waves in
-// flight.  g_tiles_per_wave > 0 overrides (clamped to QE_STREAM_TPW).
+// The stream kernels' chunk plan (qe_launch.hpp): up to QE_STREAM_TPW tiles per
+// wave; a qe_tune("tiles_per_wave") override is taken as given, 1 included.
+ChunkPlan stream_plan(uint64_t G) {
+  return chunk_plan((G + 63) / 64, num_cus(), g_tiles_per_wave, QE_STREAM_TPW, false);
+}
+
 template <int MODE, bool NTL, bool NTS>
 int launch_cv_stream(CVArgs a, hipStream_t st) {
   auto kern = k_cv_stream<S, MODE, MT, NTL, NTS>;
-  const uint64_t tiles = (a.G + 63) / 64;
-  uint64_t chunk;
-  if (g_tiles_per_wave > 0) {
-    chunk = static_cast<uint64_t>(g_tiles_per_wave);
-  } else {
-    const uint64_t waves = static_cast<uint64_t>(num_cus()) * 32;
-    chunk = (tiles + waves - 1) / waves;
-    if (chunk < 2) chunk = 2;
-  }
-  if (chunk > QE_STREAM_TPW) chunk = QE_STREAM_TPW;
-  a.chunk = static_cast<uint32_t>(chunk);
-  const uint64_t per_block = (kBlock / 64) * chunk;
-  const uint64_t blocks = (tiles + per_block - 1) / per_block;
-  if (blocks > 0x7FFFFFFFull) return QE_ERANGE;
-  hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, st, a);
+  const ChunkPlan plan = stream_plan(a.G);
+  if (plan.status) return plan.status;
+  a.chunk = plan.chunk;
+  hipLaunchKernelGGL(kern, dim3(plan.blocks), dim3(kBlock), 0, st, a);
   return hip_status(hipGetLastError());
 }
 
@@ -57,34 +48,29 @@ int launch_cv(const CVArgs &a, bool vec, hipStream_t st) {
   // it addresses each 64-group tile through buffer descriptors and needs
   // no row alignment
   const int which = g_cv_kernel >= 0 ? g_cv_kernel : 1;
-  if (which == 1) {
-    switch (g_nontemporal & 3) {
-      case 1: return launch_cv_stream<MODE, true, false>(a, st);
-      case 2: return launch_cv_stream<MODE, false, true>(a, st);
-      case 3: return launch_cv_stream<MODE, true, true>(a, st);
-      default: return launch_cv_stream<MODE, false, false>(a, st);
-    }
-  }
+  if (which == 1)
+    return with_nontemporal(g_nontemporal, [&](auto ntl, auto nts) {
+      return launch_cv_stream<MODE, ntl(), nts()>(a, st);
+    });
   if (!vec) return launch_cv_k<MODE, false, false, false>(a, st);
-  switch (g_nontemporal & 3) {
-    case 1: return launch_cv_k<MODE, true, true, false>(a, st);
-    case 2: return launch_cv_k<MODE, true, false, true>(a, st);
-    case 3: return launch_cv_k<MODE, true, true, true>(a, st);
-    default: return launch_cv_k<MODE, true, false, false>(a, st);
-  }
+  return with_nontemporal(g_nontemporal, [&](auto ntl, auto nts) {
+    return launch_cv_k<MODE, true, ntl(), nts()>(a, st);
+  });
 }
 }  // namespace
 
-#define QE_CAT2(a, b) a##b
-#define QE_CAT(a, b) QE_CAT2(a, b)
-
-int QE_CAT(dispatch_cv_, QE_S)(const CVArgs &a, int mode, bool vec, hipStream_t st) {
+// Every dispatch_<family><N> below is defined for this object's slot count
+// alone and instantiated for it at the end of its family.
+template <int N>
+int dispatch_cv(const CVArgs &a, int mode, bool vec, hipStream_t st) {
+  static_assert(N == S, "one slot count per object");
   switch (mode) {
     case 0: return launch_cv<0>(a, vec, st);
     case 1: return launch_cv<1>(a, vec, st);
     default: return launch_cv<2>(a, vec, st);
   }
 }
+template int dispatch_cv<S>(const CVArgs &, int, bool, hipStream_t);
 
 template <bool J, bool M, bool V, bool NT>
 static int launch_repl_k(const RArgs &a, hipStream_t st) {
@@ -106,50 +92,29 @@ static int launch_repl(const RArgs &a, hipStream_t st) {
 template <bool M, bool J, bool NTL, bool NTS>
 static int launch_repl_stream(RArgs a, hipStream_t st) {
   auto kern = k_repl_stream<S, M, J, MT, NTL, NTS>;
-  const uint64_t tiles = (a.G + 63) / 64;
-  uint64_t chunk;
-  if (g_tiles_per_wave > 0) {
-    chunk = static_cast<uint64_t>(g_tiles_per_wave);
-  } else {
-    const uint64_t waves = static_cast<uint64_t>(num_cus()) * 32;
-    chunk = (tiles + waves - 1) / waves;
-    if (chunk < 2) chunk = 2;
-  }
-  if (chunk > QE_STREAM_TPW) chunk = QE_STREAM_TPW;
-  a.chunk = static_cast<uint32_t>(chunk);
-  const uint64_t per_block = (kBlock / 64) * chunk;
-  const uint64_t blocks = (tiles + per_block - 1) / per_block;
-  if (blocks > 0x7FFFFFFFull) return QE_ERANGE;
-  hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, st, a);
+  const ChunkPlan plan = stream_plan(a.G);
+  if (plan.status) return plan.status;
+  a.chunk = plan.chunk;
+  hipLaunchKernelGGL(kern, dim3(plan.blocks), dim3(kBlock), 0, st, a);
   return hip_status(hipGetLastError());
 }
 
-template <bool M, bool J>
-static int launch_repl_s(const RArgs &a, hipStream_t st) {
-  switch (g_nontemporal & 3) {
-    case 1: return launch_repl_stream<M, J, true, false>(a, st);
-    case 2: return launch_repl_stream<M, J, false, true>(a, st);
-    case 3: return launch_repl_stream<M, J, true, true>(a, st);
-    default: return launch_repl_stream<M, J, false, false>(a, st);
-  }
+template <int N>
+int dispatch_repl(const RArgs &a, bool masked, bool joint, bool vec, hipStream_t st) {
+  static_assert(N == S, "one slot count per object");
+  if (g_repl_kernel != 0)  // default: stream kernel (no alignment requirement)
+    return with_quorum_form(masked, joint, [&](auto m, auto j) {
+      return with_nontemporal(g_nontemporal, [&](auto ntl, auto nts) {
+        return launch_repl_stream<m(), j(), ntl(), nts()>(a, st);
+      });
+    });
+  if (vec)
+    return with_quorum_form(masked, joint,
+                            [&](auto m, auto j) { return launch_repl<j(), m(), true>(a, st); });
+  return with_quorum_form(masked, joint,
+                          [&](auto m, auto j) { return launch_repl<j(), m(), false>(a, st); });
 }
-
-int QE_CAT(dispatch_repl_, QE_S)(const RArgs &a, bool masked, bool joint, bool vec,
-                                 hipStream_t st) {
-  if (g_repl_kernel != 0) {  // default: stream kernel (no alignment requirement)
-    if (joint) return launch_repl_s<true, true>(a, st);
-    if (masked) return launch_repl_s<true, false>(a, st);
-    return launch_repl_s<false, false>(a, st);
-  }
-  if (vec) {
-    if (joint) return launch_repl<true, true, true>(a, st);
-    if (masked) return launch_repl<false, true, true>(a, st);
-    return launch_repl<false, false, true>(a, st);
-  }
-  if (joint) return launch_repl<true, true, false>(a, st);
-  if (masked) return launch_repl<false, true, false>(a, st);
-  return launch_repl<false, false, false>(a, st);
-}
+template int dispatch_repl<S>(const RArgs &, bool, bool, bool, hipStream_t);
 
 template <int OPT>
 static int launch_elec(const EArgs &a, hipStream_t st) {
@@ -160,7 +125,9 @@ static int launch_elec(const EArgs &a, hipStream_t st) {
   return hip_status(hipGetLastError());
 }
 
-int QE_CAT(dispatch_elec_, QE_S)(const EArgs &a, hipStream_t st) {
+template <int N>
+int dispatch_elec(const EArgs &a, hipStream_t st) {
+  static_assert(N == S, "one slot count per object");
   const int opt = (a.flags & 3u) | (a.sresp ? 4 : 0) | (a.out ? 8 : 0);
   switch (opt) {
 #define QE_E(o) \
@@ -171,5 +138,6 @@ int QE_CAT(dispatch_elec_, QE_S)(const EArgs &a, hipStream_t st) {
     default: return launch_elec<15>(a, st);
   }
 }
+template int dispatch_elec<S>(const EArgs &, hipStream_t);
 
 }  // namespace qe

@@ -14,21 +14,21 @@ constexpr int S = QE_S;
 using MT = std::conditional<(S <= 8), uint8_t, uint16_t>::type;
 }  // namespace
 
-#define QE_CAT2(a, b) a##b
-#define QE_CAT(a, b) QE_CAT2(a, b)
-
 // One tile per wave (as qe_heartbeat).  With statistics the grid is capped
 // and the waves walk: every wave ends with one atomic per counter.
-int QE_CAT(dispatch_tick_, QE_S)(const TArgs &a, bool masked, bool joint, hipStream_t st) {
+template <int N>
+int dispatch_tick(const TArgs &a, bool masked, bool joint, hipStream_t st) {
+  static_assert(N == S, "one slot count per object");
   const uint64_t tiles = (a.G + 63) / 64;
   uint64_t blocks = (tiles + (kBlock / 64) - 1) / (kBlock / 64);
   const uint64_t cap = a.stats ? static_cast<uint64_t>(num_cus()) * 8 : 0x7FFFFFFFull;
   if (blocks > cap) blocks = cap;
   const dim3 grid(static_cast<unsigned>(blocks ? blocks : 1));
-  if (joint) hipLaunchKernelGGL((k_tick<S, MT, true, true>), grid, dim3(kBlock), 0, st, a);
-  else if (masked) hipLaunchKernelGGL((k_tick<S, MT, true, false>), grid, dim3(kBlock), 0, st, a);
-  else hipLaunchKernelGGL((k_tick<S, MT, false, false>), grid, dim3(kBlock), 0, st, a);
-  return hip_status(hipGetLastError());
+  return with_quorum_form(masked, joint, [&](auto m, auto j) {
+    hipLaunchKernelGGL((k_tick<S, MT, m(), j()>), grid, dim3(kBlock), 0, st, a);
+    return hip_status(hipGetLastError());
+  });
 }
+template int dispatch_tick<S>(const TArgs &, bool, bool, hipStream_t);
 
 }  // namespace qe

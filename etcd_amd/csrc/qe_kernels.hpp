@@ -15,13 +15,11 @@
 // git show bdcd377:etcd_amd/csrc/qe_progress.hpp).  A product build with any
 // of them set is refused, so a stray -D can never ship a library that
 // computes something else.
-#if !defined(QE_VARIANT_BUILD) &&                                                  \
-    (defined(QE_CQ_CHANGED_ONLY) || defined(QE_STREAM_ALL_ROWS) || defined(QE_NO_RM8) || \
-     defined(QE_RM16_WPB) || defined(QE_PSTEP_WAVES) || defined(QE_STREAM_TPW) ||        \
-     defined(QE_STREAM_WAVES) || defined(QE_JOINT_MIN_WAVES) || defined(QE_LD_AUX) ||     \
-     defined(QE_ST_AUX) || defined(QE_SEND_AUX) || defined(QE_NO_READ_OVF) ||              \
-     defined(QE_SEND16_WAVES) || defined(QE_SWITCH16_WAVES) || defined(QE_PROPOSE16_WAVES) || defined(QE_PROPOSE16_PF) || \
-     defined(QE_SEND16_ISSUE) || defined(QE_SWITCH16_ISSUE))
+#if !defined(QE_VARIANT_BUILD) &&                                                      \
+    (defined(QE_PSTEP_WAVES) || defined(QE_STREAM_TPW) || defined(QE_STREAM_WAVES) ||     \
+     defined(QE_JOINT_MIN_WAVES) || defined(QE_LD_AUX) || defined(QE_ST_AUX) ||           \
+     defined(QE_SEND_AUX) || defined(QE_SEND16_WAVES) || defined(QE_SWITCH16_WAVES) ||    \
+     defined(QE_PROPOSE16_WAVES))
 #error "A/B knob set in a product build: use scripts/build_variant*.sh (QE_VARIANT_BUILD)"
 #endif
 #include <hip/hip_runtime.h>
@@ -34,10 +32,10 @@
 
 #include "../../include/etcd_quorum.h"
 #include "qe_device.hpp"
+#include "qe_launch.hpp"
 
 namespace qe {
 
-constexpr int kBlock = 256;
 typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
 
 // ---------------------------------------------------------------------------

@@ -99,6 +99,46 @@ __device__ __forceinline__ void bst_mask(uint32_t v, rsrc_t r, uint32_t lane, bo
     __builtin_amdgcn_raw_buffer_store_b16(static_cast<uint16_t>(v), r, off, 0, 0);
 }
 
+// ---------------------------------------------------------------------------
+// Idioms the Progress kernels (and k_tick, qe_tick.hpp) share.
+// ---------------------------------------------------------------------------
+// One lane per group, one wave per 64-group tile: the lane, the wave's first
+// tile, the stride of its walk and the tile count.
+__device__ __forceinline__ void tile_walk(uint64_t G, uint32_t &lane, uint64_t &wave,
+                                          uint64_t &nwaves, uint64_t &ntiles) {
+  lane = threadIdx.x & 63;
+  wave = static_cast<uint64_t>(blockIdx.x) * (kBlock / 64) +
+         __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  nwaves = static_cast<uint64_t>(gridDim.x) * (kBlock / 64);
+  ntiles = (G + 63) / 64;
+}
+
+// A tile's row of a configuration mask (tracked, inc_mask, out_mask) clipped
+// to the S slots, for the lanes with `on` (no bytes move for the others).
+template <typename MT, int S>
+__device__ __forceinline__ uint32_t ld_slot_mask(const void *p, uint64_t g0, uint32_t n,
+                                                 uint32_t lane, bool on = true) {
+  const rsrc_t r = mk_rsrc(static_cast<const MT *>(p) + g0, n * sizeof(MT));
+  const uint32_t off = on ? lane * static_cast<uint32_t>(sizeof(MT)) : kOOB;
+  uint32_t v;
+  if constexpr (sizeof(MT) == 1)
+    v = __builtin_amdgcn_raw_buffer_load_b8(r, off, 0, 0);
+  else
+    v = __builtin_amdgcn_raw_buffer_load_b16(r, off, 0, 0);
+  return v & ((1u << S) - 1u);
+}
+
+// The ReadIndex queue: the pending count (a count above the capacity is
+// invalid input) and readOnly.lastPendingRequestCtx, the
+// context of the newest pending request, 0 with none.
+__device__ __forceinline__ uint32_t read_pending(uint32_t count, uint32_t cap) {
+  return count < cap ? count : cap;
+}
+__device__ __forceinline__ uint32_t last_pending_ctx(uint32_t count, uint32_t head, uint32_t cap) {
+  const uint32_t q = read_pending(count, cap);
+  return q ? head + q - 1u : 0u;
+}
+
 // Byte accounting of the instrumented variant (ACCT): the bytes of every
 // access the reference logic needs (field granularity, each once), i.e. the
 // algorithmic bytes of the round.  Re-reads (Match, m.Index in phase 2)
@@ -876,11 +916,7 @@ k_progress_step(PArgs a) {
   using QT = typename std::conditional<sizeof(MT) == 1, uint32_t, uint64_t>::type;
   constexpr uint32_t EW = 8 * sizeof(MT);
   constexpr uint32_t kRQ = QE_READ_QUEUE;
-#ifdef QE_NO_READ_OVF  // A/B knob: without the overflow-ring paths (ABI 5 queue only)
-  constexpr bool OVF = false;
-#else
   constexpr bool OVF = RD;  // queue entries past the word (ABI 7)
-#endif
   // statistics: per-lane counts in 32 bits (a lane sees at most one group
   // per tile), the sums in 64
   uint32_t n_groups = 0, n_adv = 0, n_viol = 0, n_read = 0;
@@ -1527,22 +1563,18 @@ k_progress_step(PArgs a) {
 // sets keep tile t+1's Progress loads in flight while tile t sends.
 constexpr int kSendTPW = 8;
 
-#ifndef QE_SEND16_ISSUE  // A/B knob: 1 = the 16-bit rings prefetched with the tile
-#define QE_SEND16_ISSUE 0
-#endif
-template <int S, bool N16>
+// (ABI 8: a wanted peer's 16-bit ring is not part of the set; ps_finish loads
+// it one peer ahead of its turn)
+template <int S>
 struct SendSet {
   uint64_t fi, li, sn;
   uint64_t nx[S];
   uint32_t pw[S];
-  // ABI 8: each wanted peer's 16-bit ring, prefetched with the tile
-  // (QE_SEND16_ISSUE; the default loads it one peer ahead in ps_finish)
-  u32x4 rg[(N16 && QE_SEND16_ISSUE) ? S : 1];
 };
 
-template <int S, bool N16>
+template <int S>
 __device__ __forceinline__ void ps_issue(const PArgs &a, uint64_t t, uint32_t lane, uint32_t w,
-                                         SendSet<S, N16> &x) {
+                                         SendSet<S> &x) {
   const uint64_t g0 = t * 64;
   const uint32_t n = tile_n(a.G, t);
   const uint32_t o8 = lane * 8, o4 = lane * 4;
@@ -1554,14 +1586,12 @@ __device__ __forceinline__ void ps_issue(const PArgs &a, uint64_t t, uint32_t la
     const uint64_t row = static_cast<uint64_t>(s) * a.stride + g0;
     x.nx[s] = bld64<kNT>(mk_rsrc(a.next + row, n * 8), bit_off(w, s, o8));
     x.pw[s] = bld32<kNT>(mk_rsrc(a.pw + row, n * 4), bit_off(w, s, o4));
-    if constexpr (N16 && QE_SEND16_ISSUE)
-      x.rg[s] = bld128(mk_rsrc(a.infl16 + row * QE_RING16_MAX_F, n * 16), bit_off(w, s, lane * 16));
   }
 }
 
 template <int S, typename MT, bool N16>
 __device__ __forceinline__ void ps_finish(const PArgs &a, uint64_t t, uint32_t lane, uint32_t w,
-                                          const SendSet<S, N16> &x) {
+                                          const SendSet<S> &x) {
   const uint64_t g0 = t * 64;
   const uint32_t n = tile_n(a.G, t);
   Acct<false> ac;
@@ -1578,23 +1608,22 @@ __device__ __forceinline__ void ps_finish(const PArgs &a, uint64_t t, uint32_t l
   // on the new Next (row form)
   xs.row = N16;
   uint32_t sent = 0, snapm = 0;
-  // (the default: each wanted peer's ring loaded one peer ahead of its turn)
+  // each wanted peer's 16-bit ring, loaded one peer ahead of its turn
   auto ring16_ld = [&](int s) -> u32x4 {
     const uint64_t row = static_cast<uint64_t>(s) * a.stride + g0;
     const bool on = ((w >> s) & 1u) && ((x.pw[s] >> QE_PW_COUNT_SHIFT) & 0xFFu) != 0;
     return bld128(mk_rsrc(a.infl16 + row * QE_RING16_MAX_F, n * 16), on ? lane * 16 : kOOB);
   };
   u32x4 raw_nx = {0, 0, 0, 0};
-  if constexpr (N16 && !QE_SEND16_ISSUE) raw_nx = ring16_ld(0);
+  if constexpr (N16) raw_nx = ring16_ld(0);
 #pragma unroll
   for (int s = 0; s < S; s++) {
     const uint64_t row = static_cast<uint64_t>(s) * a.stride + g0;
     const bool on = (w >> s) & 1u;
-    u32x4 raw = raw_nx;
-    if constexpr (N16 && !QE_SEND16_ISSUE) {
+    const u32x4 raw = raw_nx;
+    if constexpr (N16) {
       if (s + 1 < S) raw_nx = ring16_ld(s + 1);
     }
-    if constexpr (N16 && QE_SEND16_ISSUE) raw = x.rg[s];
     PR p;
     p.match = 0;
     p.next = x.nx[s];
@@ -1655,13 +1684,13 @@ k_progress_send(PArgs a) {
   // tile k of the chunk, or past the end (no loads, no stores, want 0)
   auto tix = [&](uint32_t k) -> uint64_t { return k < nt ? t0 + k : ntiles; };
   auto want_of = [&](uint32_t k) -> uint32_t { return k < nt ? lds_w[wv][k][lane] : 0u; };
-  SendSet<S, N16> xa, xb;
-  ps_issue<S, N16>(a, tix(0), lane, want_of(0), xa);
+  SendSet<S> xa, xb;
+  ps_issue<S>(a, tix(0), lane, want_of(0), xa);
   for (uint32_t k = 0; k < nt; k += 2) {
-    ps_issue<S, N16>(a, tix(k + 1), lane, want_of(k + 1), xb);
+    ps_issue<S>(a, tix(k + 1), lane, want_of(k + 1), xb);
     __builtin_amdgcn_sched_barrier(0);  // keep the prefetch ahead of the sends
     ps_finish<S, MT, N16>(a, tix(k), lane, want_of(k), xa);
-    ps_issue<S, N16>(a, tix(k + 2), lane, want_of(k + 2), xa);
+    ps_issue<S>(a, tix(k + 2), lane, want_of(k + 2), xa);
     __builtin_amdgcn_sched_barrier(0);
     ps_finish<S, MT, N16>(a, tix(k + 1), lane, want_of(k + 1), xb);
   }
@@ -1685,9 +1714,6 @@ constexpr uint64_t kPropSalt = 0x9E6C63D0676A9A99ull;
 #ifndef QE_PROPOSE16_WAVES  // A/B knob (1 = no budget: 149 VGPRs, 3 waves)
 #define QE_PROPOSE16_WAVES 4
 #endif
-#ifndef QE_PROPOSE16_PF  // A/B knob: 0 = each ring loaded at its peer's turn
-#define QE_PROPOSE16_PF 1
-#endif
 template <int S, typename MT, bool MASKED, bool JOINT, bool ACCT, bool N16 = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(N16 ? QE_PROPOSE16_WAVES : 1))) void
 k_propose(PArgs a) {
@@ -1695,11 +1721,9 @@ k_propose(PArgs a) {
   constexpr uint32_t MB = sizeof(MT);
   uint64_t cnt[Q_N] = {0, 0, 0, 0};
   Acct<ACCT> ac;
-  const uint32_t lane = threadIdx.x & 63;
-  const uint64_t wave = static_cast<uint64_t>(blockIdx.x) * (kBlock / 64) +
-                        __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint64_t nwaves = static_cast<uint64_t>(gridDim.x) * (kBlock / 64);
-  const uint64_t ntiles = (a.G + 63) / 64;
+  uint32_t lane;
+  uint64_t wave, nwaves, ntiles;
+  tile_walk(a.G, lane, wave, nwaves, ntiles);
   const uint64_t maxu = a.max_unc ? a.max_unc : ~0ull;  // 0 = noLimit
   const bool app_only = (a.prop_flags & QE_PROP_APPEND_ONLY) != 0;
   // Loads in three stages per tile, software-pipelined across the wave's
@@ -1734,14 +1758,11 @@ k_propose(PArgs a) {
     const uint64_t g0 = t * 64;
     const bool prop = x.ne != 0;
     const uint32_t o1 = prop ? lane : kOOB;
-    y.trk = a.tracked ? (ld_mask_r<MT>(mk_rsrc(static_cast<const MT *>(a.tracked) + g0, n * MB), lane) & kFull)
-                      : kFull;
+    y.trk = a.tracked ? ld_slot_mask<MT, S>(a.tracked, g0, n, lane) : kFull;
     y.self = a.self_slot ? bld8(mk_rsrc(a.self_slot + g0, n), o1) : 0xFFu;
     y.ltr = a.transferee ? bld8(mk_rsrc(a.transferee + g0, n), o1) : 0xFFu;
-    y.mi = MASKED ? (ld_mask_r<MT>(mk_rsrc(static_cast<const MT *>(a.inc) + g0, n * MB), lane) & kFull)
-                  : kFull;
-    y.mo = JOINT ? (ld_mask_r<MT>(mk_rsrc(static_cast<const MT *>(a.out) + g0, n * MB), lane) & kFull)
-                 : 0u;
+    y.mi = MASKED ? ld_slot_mask<MT, S>(a.inc, g0, n, lane) : kFull;
+    y.mo = JOINT ? ld_slot_mask<MT, S>(a.out, g0, n, lane) : 0u;
     y.sz = a.prop_payload ? bld64(mk_rsrc(a.prop_payload + g0, n * 8), prop ? lane * 8 : kOOB) : 0;
     y.ncc = a.max_cc ? bld8(mk_rsrc(a.cc_count + g0, n), o1) : 0u;
     y.us = bld64(opt_rsrc(a.unc, g0, n), prop ? lane * 8 : kOOB);
@@ -1901,14 +1922,14 @@ k_propose(PArgs a) {
           return bld128(mk_rsrc(a.infl16 + row * QE_RING16_MAX_F, n * 16), on ? lane * 16 : kOOB);
         };
         u32x4 raw_nx = {0, 0, 0, 0};
-        if constexpr (N16 && QE_PROPOSE16_PF) raw_nx = ring16_ld(0);
+        if constexpr (N16) raw_nx = ring16_ld(0);
 #pragma unroll
         for (int s = 0; s < S; s++) {
           const uint64_t row = static_cast<uint64_t>(s) * a.stride + g0;
           const bool is_self = ok && self == static_cast<uint32_t>(s);
           const bool tgt = ok && !app_only && ((trk >> s) & 1u) && self != static_cast<uint32_t>(s);
-          u32x4 raw_cur = raw_nx;
-          if constexpr (N16 && QE_PROPOSE16_PF) {
+          const u32x4 raw = raw_nx;
+          if constexpr (N16) {
             if (s + 1 < S) raw_nx = ring16_ld(s + 1);
           }
           PR p;
@@ -1934,8 +1955,6 @@ k_propose(PArgs a) {
           // held entries (never, from becomeLeader on: nothing is sent to it)
           uint32_t nws_s = nws;
           if constexpr (N16) {
-            const bool rl = (tgt || is_self) && p.count > 0;
-            const u32x4 raw = QE_PROPOSE16_PF ? raw_cur : bld128(x.r16, rl ? lane * 16 : kOOB);
             PR q = p;
             if (is_self) q = ps;
             ring_append_n16(q, x, run, tgt || is_self, nx[s], rep_old, raw, a.FP);
@@ -2005,9 +2024,6 @@ constexpr uint64_t kSwitchSalt = 0x2545F4914F6CDD1Dull;
 #ifndef QE_SWITCH16_WAVES  // A/B knob: the 16-bit switch kernel's wave budget (1 = none)
 #define QE_SWITCH16_WAVES 1
 #endif
-#ifndef QE_SWITCH16_ISSUE  // A/B knob: 1 = the 16-bit rings prefetched with round trip B
-#define QE_SWITCH16_ISSUE 0
-#endif
 template <int S, typename MT, bool MASKED, bool JOINT, bool ACCT, bool N16 = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(N16 ? QE_SWITCH16_WAVES : 1))) void
 k_switch_config(PArgs a) {
@@ -2015,11 +2031,9 @@ k_switch_config(PArgs a) {
   constexpr uint32_t MB = sizeof(MT);
   uint64_t cnt[Q_N] = {0, 0, 0, 0};
   Acct<ACCT> ac;
-  const uint32_t lane = threadIdx.x & 63;
-  const uint64_t wave = static_cast<uint64_t>(blockIdx.x) * (kBlock / 64) +
-                        __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint64_t nwaves = static_cast<uint64_t>(gridDim.x) * (kBlock / 64);
-  const uint64_t ntiles = (a.G + 63) / 64;
+  uint32_t lane;
+  uint64_t wave, nwaves, ntiles;
+  tile_walk(a.G, lane, wave, nwaves, ntiles);
   struct SA {
     uint32_t sw, self, trk, mi, mo, ltr;
     uint64_t c0;  // committed of every group (the statistics cover it)
@@ -2072,9 +2086,6 @@ k_switch_config(PArgs a) {
     const uint32_t vm = h.mi | h.mo;
     uint64_t mt[S], nx[S];
     uint32_t pw[S];
-    // ABI 8: the 16-bit rings of the targets, prefetched with round trip B
-    // (QE_SWITCH16_ISSUE; the default loads each one target ahead)
-    u32x4 rg[(N16 && QE_SWITCH16_ISSUE) ? S : 1];
 #pragma unroll
     for (int s = 0; s < S; s++) {
       const uint64_t row = static_cast<uint64_t>(s) * a.stride + g0;
@@ -2082,8 +2093,6 @@ k_switch_config(PArgs a) {
       mt[s] = bld64(mk_rsrc(a.match + row, n * 8), bit_off(go ? vm : 0u, s, o8));
       nx[s] = bld64(mk_rsrc(a.next + row, n * 8), bit_off(tgt, s, o8));
       pw[s] = bld32(mk_rsrc(a.pw + row, n * 4), bit_off(tgt, s, o4));
-      if constexpr (N16 && QE_SWITCH16_ISSUE)
-        rg[s] = bld128(mk_rsrc(a.infl16 + row * QE_RING16_MAX_F, n * 16), bit_off(tgt, s, lane * 16));
     }
     // round trip A of the wave's next tile, before this tile's stores
     load_a(t + nwaves, ha);
@@ -2120,16 +2129,15 @@ k_switch_config(PArgs a) {
         return bld128(mk_rsrc(a.infl16 + row * QE_RING16_MAX_F, n * 16), on ? lane * 16 : kOOB);
       };
       u32x4 raw_nx = {0, 0, 0, 0};
-      if constexpr (N16 && !QE_SWITCH16_ISSUE) raw_nx = ring16_ld(0);
+      if constexpr (N16) raw_nx = ring16_ld(0);
 #pragma unroll
       for (int s = 0; s < S; s++) {
         const uint64_t row = static_cast<uint64_t>(s) * a.stride + g0;
         const bool on = ((tg >> s) & 1u) != 0;
-        u32x4 raw = raw_nx;
-        if constexpr (N16 && !QE_SWITCH16_ISSUE) {
+        const u32x4 raw = raw_nx;
+        if constexpr (N16) {
           if (s + 1 < S) raw_nx = ring16_ld(s + 1);
         }
-        if constexpr (N16 && QE_SWITCH16_ISSUE) raw = rg[s];
         PR p;
         p.match = mt[s];
         p.next = nx[s];
@@ -2207,7 +2215,6 @@ constexpr uint64_t kLeaderSalt = 0x6A09E667BB67AE85ull;
 template <int S, typename MT, bool MASKED, bool JOINT>
 __global__ __launch_bounds__(kBlock) void k_become_leader(PArgs a) {
   constexpr uint32_t kFull = (1u << S) - 1u;
-  constexpr uint32_t MB = sizeof(MT);
   uint64_t cnt[Q_N] = {0, 0, 0, 0};
   const uint32_t lane = threadIdx.x & 63;
   const uint64_t wave = static_cast<uint64_t>(blockIdx.x) * (kBlock / 64) +
@@ -2223,13 +2230,9 @@ __global__ __launch_bounds__(kBlock) void k_become_leader(PArgs a) {
     const bool el = a.bl_elected ? bld8(mk_rsrc(a.bl_elected + g0, n), lane) != 0 : live;
     const uint32_t o1 = el ? lane : kOOB;
     const uint32_t self = a.self_slot ? bld8(mk_rsrc(a.self_slot + g0, n), o1) : 0xFFu;
-    const uint32_t trk =
-        a.tracked ? (ld_mask_r<MT>(mk_rsrc(static_cast<const MT *>(a.tracked) + g0, n * MB), lane) & kFull)
-                  : kFull;
-    const uint32_t mi = MASKED ? (ld_mask_r<MT>(mk_rsrc(static_cast<const MT *>(a.inc) + g0, n * MB), lane) & kFull)
-                               : kFull;
-    const uint32_t mo = JOINT ? (ld_mask_r<MT>(mk_rsrc(static_cast<const MT *>(a.out) + g0, n * MB), lane) & kFull)
-                              : 0u;
+    const uint32_t trk = a.tracked ? ld_slot_mask<MT, S>(a.tracked, g0, n, lane) : kFull;
+    const uint32_t mi = MASKED ? ld_slot_mask<MT, S>(a.inc, g0, n, lane) : kFull;
+    const uint32_t mo = JOINT ? ld_slot_mask<MT, S>(a.out, g0, n, lane) : 0u;
     const rsrc_t r_li = mk_rsrc(a.last_index + g0, n * 8), r_c = mk_rsrc(a.committed + g0, n * 8);
     const uint64_t li = bld64(r_li, el ? o8 : kOOB);
     const uint64_t c0 = bld64(r_c, o8);
@@ -2281,8 +2284,7 @@ __global__ __launch_bounds__(kBlock) void k_become_leader(PArgs a) {
       if (a.read_acks) {  // newReadOnly: nothing pending, the old numbers never reused
         const uint32_t qn = bld8(mk_rsrc(a.read_count + g0, n), go ? lane : kOOB);
         const uint32_t qh = bld32(mk_rsrc(a.read_head + g0, n * 4), go ? o4 : kOOB);
-        const uint32_t q = qn < a.read_cap ? qn : a.read_cap;
-        bst32(qh + q, mk_rsrc(a.read_head + g0, n * 4), go ? o4 : kOOB);
+        bst32(qh + read_pending(qn, a.read_cap), mk_rsrc(a.read_head + g0, n * 4), go ? o4 : kOOB);
         bst8(0u, mk_rsrc(a.read_count + g0, n), go ? lane : kOOB);
       }
       if (a.bl_pci) bst64(li, mk_rsrc(a.bl_pci + g0, n * 8), k8);
@@ -2371,11 +2373,9 @@ __global__ __launch_bounds__(kBlock) void k_become_leader(PArgs a) {
 template <int S, typename MT>
 __global__ __launch_bounds__(kBlock) void k_heartbeat(PArgs a) {
   constexpr uint32_t kFull = (1u << S) - 1u;
-  const uint32_t lane = threadIdx.x & 63;
-  const uint64_t wave = static_cast<uint64_t>(blockIdx.x) * (kBlock / 64) +
-                        __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint64_t nwaves = static_cast<uint64_t>(gridDim.x) * (kBlock / 64);
-  const uint64_t ntiles = (a.G + 63) / 64;
+  uint32_t lane;
+  uint64_t wave, nwaves, ntiles;
+  tile_walk(a.G, lane, wave, nwaves, ntiles);
   // a tile's masks, committed and ReadIndex queue head (past the end: zeros)
   struct HB {
     uint32_t trk, self, qn, qh;
@@ -2384,9 +2384,7 @@ __global__ __launch_bounds__(kBlock) void k_heartbeat(PArgs a) {
   auto load_h = [&](uint64_t t, HB &h) {
     const uint32_t n = t < ntiles ? tile_n(a.G, t) : 0u;
     const uint64_t g0 = t * 64;
-    h.trk = a.tracked ? (ld_mask_r<MT>(mk_rsrc(static_cast<const MT *>(a.tracked) + g0, n * sizeof(MT)), lane) &
-                         kFull)
-                      : kFull;
+    h.trk = a.tracked ? ld_slot_mask<MT, S>(a.tracked, g0, n, lane) : kFull;
     h.self = a.self_slot ? bld8<kNT>(mk_rsrc(a.self_slot + g0, n), lane) : 0xFFu;
     h.c = bld64<kNT>(mk_rsrc(a.committed + g0, n * 8), lane * 8);
     h.qn = h.qh = 0;
@@ -2416,9 +2414,7 @@ __global__ __launch_bounds__(kBlock) void k_heartbeat(PArgs a) {
     }
     load_h(t + nwaves, h);  // the wave's next tile, before this tile's stores
     if (a.hb_ctx) {
-      const uint32_t q = qn < a.read_cap ? qn : a.read_cap;
-      const uint32_t cx = q ? qh + q - 1u : 0u;  // lastPendingRequestCtx
-      bst32<kNT>(cx, mk_rsrc(a.hb_ctx + g0, n * 4), lane * 4);
+      bst32<kNT>(last_pending_ctx(qn, qh, a.read_cap), mk_rsrc(a.hb_ctx + g0, n * 4), lane * 4);
     }
 #pragma unroll
     for (int s = 0; s < S; s++) {
@@ -2480,11 +2476,7 @@ __device__ __forceinline__ void cq_finish(const PArgs &a, uint64_t t, uint32_t l
     // a row some lane changes is stored for every tracked lane (unchanged
     // words rewritten as loaded): whole 64-B sectors instead of the partial
     // ones of changed words only, 0.137 -> 0.120 ms (profiles/r03/cq_fullrow_ab.txt)
-#ifdef QE_CQ_CHANGED_ONLY  // A/B knob: store only the changed words
-    const bool wf = wr;
-#else
     const bool wf = (trk >> s) & 1u;
-#endif
     if (__builtin_amdgcn_ballot_w64(wr))
       bst32(nw, mk_rsrc(a.pw + static_cast<uint64_t>(s) * a.stride + g0, n * 4),
             wf ? lane * 4 : kOOB);
@@ -2572,11 +2564,9 @@ __global__ __launch_bounds__(kBlock) void k_read_index(PArgs a) {
   using QT = typename std::conditional<sizeof(MT) == 1, uint32_t, uint64_t>::type;
   constexpr uint32_t EW = 8 * sizeof(MT);
   constexpr uint32_t kRQ = QE_READ_QUEUE;
-  const uint32_t lane = threadIdx.x & 63;
-  const uint64_t wave = static_cast<uint64_t>(blockIdx.x) * (kBlock / 64) +
-                        __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint64_t nwaves = static_cast<uint64_t>(gridDim.x) * (kBlock / 64);
-  const uint64_t ntiles = (a.G + 63) / 64;
+  uint32_t lane;
+  uint64_t wave, nwaves, ntiles;
+  tile_walk(a.G, lane, wave, nwaves, ntiles);
   const uint32_t cap = a.read_cap;
   for (uint64_t t = wave; t < ntiles; t += nwaves) {
     const uint64_t g0 = t * 64;
@@ -2586,14 +2576,8 @@ __global__ __launch_bounds__(kBlock) void k_read_index(PArgs a) {
     uint32_t res = QE_RI_NONE, ctx = 0;
     uint64_t c = 0;
     if (__builtin_amdgcn_ballot_w64(req)) {
-      const uint32_t mi =
-          MASKED ? (ld_mask_r<MT>(mk_rsrc(static_cast<const MT *>(a.inc) + g0, n * sizeof(MT)), lane) &
-                    kFull)
-                 : kFull;
-      const uint32_t mo =
-          JOINT ? (ld_mask_r<MT>(mk_rsrc(static_cast<const MT *>(a.out) + g0, n * sizeof(MT)), lane) &
-                   kFull)
-                : 0u;
+      const uint32_t mi = MASKED ? ld_slot_mask<MT, S>(a.inc, g0, n, lane) : kFull;
+      const uint32_t mo = JOINT ? ld_slot_mask<MT, S>(a.out, g0, n, lane) : 0u;
       const uint32_t ro = req ? o8 : kOOB;
       c = bld64(mk_rsrc(a.committed + g0, n * 8), ro);
       const uint64_t ts = bld64(mk_rsrc(a.term_start + g0, n * 8), ro);

@@ -80,14 +80,12 @@ __device__ __forceinline__ void st_issue(const CVArgs &a, uint64_t t, uint32_t l
   for (int s = 0; s < S; s++) {
     const rsrc_t r = mk_rsrc(a.match + s * a.stride + tile0, n * 8);
     const uint32_t o = MODE == 0 ? off : bit_off(use, s, off);
-#ifndef QE_STREAM_ALL_ROWS  // A/B knob: issue every slot row's load
     // slots >= top (scalar) hold no voter of the chunk: no instruction at all
     // (a fully dropped load still costs an issue slot of the memory path)
     if (MODE != 0 && static_cast<uint32_t>(s) >= top) {
       v[s] = 0;
       continue;
     }
-#endif
     v[s] = __builtin_bit_cast(uint64_t, __builtin_amdgcn_raw_buffer_load_b64(r, o, 0, NTL ? 2 : 0));
   }
   const MT *lp = static_cast<const MT *>(a.learner), *vp = static_cast<const MT *>(a.voted);

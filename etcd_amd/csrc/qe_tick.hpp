@@ -61,12 +61,9 @@ struct TArgs {
 
 int hip_status(hipError_t e);
 
-#define QE_DECL_TICK(n) \
-  int dispatch_tick_##n(const TArgs &a, bool masked, bool joint, hipStream_t st);
-QE_DECL_TICK(1) QE_DECL_TICK(2) QE_DECL_TICK(3) QE_DECL_TICK(4) QE_DECL_TICK(5) QE_DECL_TICK(6)
-QE_DECL_TICK(7) QE_DECL_TICK(8) QE_DECL_TICK(9) QE_DECL_TICK(10) QE_DECL_TICK(11)
-QE_DECL_TICK(12) QE_DECL_TICK(13) QE_DECL_TICK(14) QE_DECL_TICK(15) QE_DECL_TICK(16)
-#undef QE_DECL_TICK
+// defined in qe_inst_tick.hip and instantiated there for the object's QE_S
+template <int S>
+int dispatch_tick(const TArgs &a, bool masked, bool joint, hipStream_t st);
 
 constexpr uint32_t kDrawStream = 0x7131;  // hash4 stream of the timeout draw
 constexpr uint32_t kTimerMax = 0xFFFFu;   // the counters saturate here
@@ -78,16 +75,6 @@ __device__ __forceinline__ uint32_t bld16(rsrc_t r, uint32_t off) {
 template <int AUX = QE_ST_AUX>
 __device__ __forceinline__ void bst16(uint32_t v, rsrc_t r, uint32_t off) {
   __builtin_amdgcn_raw_buffer_store_b16(static_cast<uint16_t>(v), r, off, 0, AUX);
-}
-
-// ld_mask_r for the lanes with `on` (no bytes move for the others)
-template <typename MT>
-__device__ __forceinline__ uint32_t ld_mask_on(rsrc_t r, uint32_t lane, bool on) {
-  const uint32_t off = on ? lane * static_cast<uint32_t>(sizeof(MT)) : kOOB;
-  if constexpr (sizeof(MT) == 1)
-    return __builtin_amdgcn_raw_buffer_load_b8(r, off, 0, 0);
-  else
-    return __builtin_amdgcn_raw_buffer_load_b16(r, off, 0, 0);
 }
 
 // resetRandomizedElectionTimeout (raft/raft.go:1718-1720): electionTimeout +
@@ -104,11 +91,9 @@ template <int S, typename MT, bool MASKED, bool JOINT>
 __global__ __launch_bounds__(kBlock) void k_tick(TArgs a) {
   constexpr uint32_t kFull = (1u << S) - 1u;
   uint64_t cnt[T_N] = {0, 0, 0, 0};
-  const uint32_t lane = threadIdx.x & 63;
-  const uint64_t wave = static_cast<uint64_t>(blockIdx.x) * (kBlock / 64) +
-                        __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint64_t nwaves = static_cast<uint64_t>(gridDim.x) * (kBlock / 64);
-  const uint64_t ntiles = (a.G + 63) / 64;
+  uint32_t lane;
+  uint64_t wave, nwaves, ntiles;
+  tile_walk(a.G, lane, wave, nwaves, ntiles);
   const bool cq_on = (a.flags & QE_TICK_CHECK_QUORUM) != 0;
   const bool want_ctx = a.hb_ctx && a.read_acks;
   for (uint64_t t = wave; t < ntiles; t += nwaves) {
@@ -148,19 +133,13 @@ __global__ __launch_bounds__(kBlock) void k_tick(TArgs a) {
       uint64_t c = 0;
       const bool need = cand || cqf || beatp;
       if (__builtin_amdgcn_ballot_w64(need)) {
-        if (a.tracked)
-          trk = ld_mask_on<MT>(mk_rsrc(static_cast<const MT *>(a.tracked) + g0, n * sizeof(MT)),
-                               lane, need) & kFull;
+        if (a.tracked) trk = ld_slot_mask<MT, S>(a.tracked, g0, n, lane, need);
         if (a.self_slot) self = bld8<kNT>(mk_rsrc(a.self_slot + g0, n), need ? lane : kOOB);
       }
       if (__builtin_amdgcn_ballot_w64(cand || cqf)) {
         const bool on = cand || cqf;
-        if constexpr (MASKED)
-          mi = ld_mask_on<MT>(mk_rsrc(static_cast<const MT *>(a.inc) + g0, n * sizeof(MT)), lane,
-                              on) & kFull;
-        if constexpr (JOINT)
-          mo = ld_mask_on<MT>(mk_rsrc(static_cast<const MT *>(a.out) + g0, n * sizeof(MT)), lane,
-                              on) & kFull;
+        if constexpr (MASKED) mi = ld_slot_mask<MT, S>(a.inc, g0, n, lane, on);
+        if constexpr (JOINT) mo = ld_slot_mask<MT, S>(a.out, g0, n, lane, on);
         nc = bld8<kNT>(opt_rsrc(a.no_campaign, g0, n), cand ? lane : kOOB);
       }
       if (a.transferee && __builtin_amdgcn_ballot_w64(fire))
@@ -227,8 +206,7 @@ __global__ __launch_bounds__(kBlock) void k_tick(TArgs a) {
       he = beat ? 0u : he;
       act |= beat ? QE_TICK_BEAT : 0u;
       hb_to = beat ? hb_to : 0u;
-      const uint32_t q = qn < a.read_cap ? qn : a.read_cap;
-      ctx = q ? qh + q - 1u : 0u;  // lastPendingRequestCtx
+      ctx = last_pending_ctx(qn, qh, a.read_cap);
       // ---- 4. the stores of what the timers fired ----
       if (__builtin_amdgcn_ballot_w64(cqf)) {
 #pragma unroll

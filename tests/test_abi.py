@@ -179,6 +179,188 @@ def test_argument_errors_without_gpu():
     assert L.qe_election_steps(C.byref(st), C.byref(p), None, None) == _lib.QE_ERANGE
 
 
+_V = C.c_void_p(64)  # a non-null pointer no case ever reaches a kernel with
+_INV, _RNG, _OK = _lib.QE_EINVAL, _lib.QE_ERANGE, _lib.QE_OK
+_REQUIRED = ["match", "next", "pending_snapshot", "peer", "infl_lo", "infl_hi", "committed",
+             "term_start", "first_index", "last_index"]
+_RUNS = ["run_first", "run_term", "run_count"]
+_QUEUE = dict(read_acks=_V, read_head=_V, read_count=_V)
+_EMPTY = dict(num_groups=0, stride=0)
+
+
+def _progress(**over):
+    """A qe_progress every entry point accepts (4 groups, 3 slots), then `over`."""
+    kw = dict(num_groups=4, num_slots=3, inflight_cap=4, stride=4, log_runs=1, self_slot=_V)
+    kw.update({k: _V for k in _REQUIRED + _RUNS})
+    kw.update(over)
+    return _lib.QeProgress(**kw)
+
+
+def _ref(s):
+    return None if s is None else C.byref(s)
+
+
+def _msgs(**o):
+    return _lib.QePeerMsgs(**{**dict(type=_V, index=_V, reject_hint=_V, log_term=_V), **o})
+
+
+def _props(**o):
+    return _lib.QeProposals(**{**dict(num_entries=_V, result=_V), **o})
+
+
+def _leader(**o):
+    return _lib.QeLeader(**{**dict(term=_V, result=_V), **o})
+
+
+def _timers(**o):
+    kw = dict(state=_V, timer=_V, randomized_timeout=_V, election_timeout=10,
+              heartbeat_timeout=1, flags=_lib.QE_TICK_CHECK_QUORUM, ticks=1)
+    return _lib.QeTimers(**{**kw, **o})
+
+
+# entry point -> call(L, qe_progress or None, **what the case overrides beside it)
+_ENTRY = {
+    "step": lambda L, p, m=_msgs(): L.qe_progress_step(_ref(p), _ref(m), None, None),
+    "send": lambda L, p, want=_V: L.qe_progress_send(_ref(p), want, 0, None, None, None),
+    "propose": lambda L, p, prop=_props(): L.qe_propose(_ref(p), _ref(prop), None, None),
+    "switch_config": lambda L, p, sw=_lib.QeSwitch(result=_V):
+        L.qe_switch_config(_ref(p), _ref(sw), None, None),
+    "become_leader": lambda L, p, l=_leader(): L.qe_become_leader(_ref(p), _ref(l), None, None),
+    "heartbeat": lambda L, p, commit=_V: L.qe_heartbeat(_ref(p), commit, None, None, None),
+    "tick": lambda L, p, t=_timers(), out=_lib.QeTickOut(action=_V):
+        L.qe_tick(_ref(p), _ref(t), _ref(out), None, None),
+    "read_index": lambda L, p, request=_V, result=_V, lease=1:
+        L.qe_read_index(_ref(p), request, None, lease, result, None, None, None),
+    "check_quorum": lambda L, p: L.qe_check_quorum(_ref(p), None, None, None),
+}
+_FULL = ["step", "send", "propose", "switch_config", "become_leader"]  # the whole struct
+_PARTIAL = ["heartbeat", "tick", "read_index", "check_quorum"]
+_QUEUED = ["heartbeat", "tick", "read_index"]  # the partial ones that read the queue
+
+
+def _status_cases():
+    """(entry, qe_progress overrides or None for a null struct, other overrides,
+    expected status).  No case may pass validation with groups in the batch."""
+    cs = []
+    for e in _FULL + _PARTIAL:
+        cs += [(e, None, {}, _INV), (e, dict(num_slots=0), {}, _INV),
+               (e, dict(num_slots=17), {}, _INV), (e, dict(reserved=1), {}, _INV),
+               (e, dict(reserved2=1), {}, _INV), (e, dict(stride=3), {}, _INV),
+               (e, _EMPTY, {}, _OK)]
+    for e in _FULL + ["tick", "read_index", "check_quorum"]:
+        cs.append((e, dict(out_mask=_V), {}, _INV))
+    for e in _FULL:
+        cs += [(e, dict(reserved3=1), {}, _INV), (e, dict(inflight_cap=0), {}, _RNG),
+               (e, dict(inflight_cap=256), {}, _RNG), (e, dict(log_runs=17), {}, _RNG),
+               (e, dict(read_cap=3), {}, _RNG), (e, dict(read_cap=256), {}, _RNG),
+               (e, dict(read_cap=5, **_QUEUE), {}, _INV),  # a long queue without read_ovf
+               (e, dict(infl16=_V, inflight_cap=9), {}, _RNG),
+               (e, dict(infl16=_V, num_slots=10), {}, _RNG),
+               (e, dict(infl16=_V, log_runs=5), {}, _RNG),
+               # two rules at once: the earlier one wins
+               (e, dict(inflight_cap=0, stride=3), {}, _RNG),
+               (e, dict(num_slots=17, inflight_cap=0), {}, _INV),
+               (e, dict(log_runs=17, match=None), {}, _RNG),
+               (e, dict(read_cap=256, reserved3=1), {}, _INV),
+               # the empty batch is still checked for its shape
+               (e, dict(log_runs=17, **_EMPTY), {}, _RNG)]
+        cs += [(e, {k: None}, {}, _INV) for k in _REQUIRED + _RUNS]
+    cs += [
+        ("step", {}, dict(m=None), _INV), ("step", _EMPTY, dict(m=None), _INV),
+        ("step", {}, dict(m=_msgs(type=None)), _INV), ("step", {}, dict(m=_msgs(index=None)), _INV),
+        ("step", {}, dict(m=_msgs(reject_hint=None)), _INV),
+        ("step", {}, dict(m=_msgs(log_term=None)), _INV),
+        ("step", dict(log_runs=0), {}, _INV),
+        ("step", dict(read_acks=_V), {}, _INV), ("step", dict(read_acks=_V, read_head=_V), {}, _INV),
+        ("step", dict(read_acks=_V, read_count=_V), {}, _INV),
+        ("step", dict(read_acks=_V, read_cap=256), {}, _RNG),
+        ("send", {}, dict(want=None), _INV), ("send", _EMPTY, dict(want=None), _OK),
+        ("propose", {}, dict(prop=None), _INV), ("propose", _EMPTY, dict(prop=None), _INV),
+        ("propose", {}, dict(prop=_props(flags=2)), _INV),
+        ("propose", {}, dict(prop=_props(max_cc=9)), _RNG),
+        ("propose", _EMPTY, dict(prop=_props(max_cc=9)), _RNG),
+        ("propose", {}, dict(prop=_props(num_entries=None)), _INV),
+        ("propose", {}, dict(prop=_props(result=None)), _INV),
+        ("propose", dict(self_slot=None), {}, _INV),
+        ("propose", {}, dict(prop=_props(max_cc=1)), _INV),
+        ("propose", {}, dict(prop=_props(max_uncommitted=1)), _INV),
+        ("propose", dict(inflight_cap=0), dict(prop=None), _RNG),
+        ("switch_config", {}, dict(sw=None), _INV),
+        ("switch_config", {}, dict(sw=_lib.QeSwitch()), _INV),
+        ("switch_config", _EMPTY, dict(sw=_lib.QeSwitch()), _OK),
+        ("become_leader", {}, dict(l=None), _INV),
+        ("become_leader", {}, dict(l=_leader(reserved=1)), _INV),
+        ("become_leader", _EMPTY, dict(l=_leader(flags=2)), _INV),
+        ("become_leader", {}, dict(l=_leader(term=None)), _INV),
+        ("become_leader", {}, dict(l=_leader(result=None)), _INV),
+        ("become_leader", dict(self_slot=None), {}, _INV),
+        ("heartbeat", dict(match=None), {}, _INV), ("heartbeat", dict(committed=None), {}, _INV),
+        ("heartbeat", {}, dict(commit=None), _INV),
+        ("heartbeat", dict(reserved3=1, read_cap=3, **_EMPTY), {}, _OK),
+        ("tick", {}, dict(t=None), _INV), ("tick", {}, dict(out=None), _INV),
+        ("tick", _EMPTY, dict(t=_timers(election_timeout=0)), _OK),
+        ("tick", {}, dict(t=_timers(state=None)), _INV), ("tick", {}, dict(t=_timers(timer=None)), _INV),
+        ("tick", {}, dict(t=_timers(randomized_timeout=None)), _INV),
+        ("tick", {}, dict(out=_lib.QeTickOut()), _INV),
+        ("tick", {}, dict(t=_timers(election_timeout=0)), _INV),
+        ("tick", {}, dict(t=_timers(election_timeout=32769)), _INV),
+        ("tick", {}, dict(t=_timers(heartbeat_timeout=0)), _INV),
+        ("tick", {}, dict(t=_timers(heartbeat_timeout=65536)), _INV),
+        ("tick", {}, dict(t=_timers(flags=2)), _INV), ("tick", {}, dict(t=_timers(ticks=2)), _INV),
+        ("tick", dict(peer=None), {}, _INV),
+        ("tick", dict(match=None), dict(out=_lib.QeTickOut(action=_V, hb_commit=_V)), _INV),
+        ("tick", dict(committed=None), dict(out=_lib.QeTickOut(action=_V, hb_commit=_V)), _INV),
+        ("tick", dict(stride=3), dict(t=_timers(flags=0), out=_lib.QeTickOut(action=_V, hb_commit=_V)),
+         _INV),
+        ("read_index", {}, dict(request=None), _INV), ("read_index", {}, dict(result=None), _INV),
+        ("read_index", dict(committed=None), {}, _INV), ("read_index", dict(term_start=None), {}, _INV),
+        ("read_index", dict(last_index=None), {}, _INV),
+        ("read_index", {}, dict(lease=0), _INV),  # ReadOnlySafe needs the queue
+        ("read_index", dict(read_acks=_V, read_head=_V), dict(lease=0), _INV),
+        ("read_index", dict(read_cap=256), dict(lease=0), _INV),
+        ("read_index", dict(read_cap=256), {}, _RNG),
+        ("read_index", dict(reserved3=1, **_EMPTY), {}, _OK),
+        ("check_quorum", dict(peer=None), {}, _INV),
+        ("check_quorum", dict(stride=3, out_mask=_V), {}, _INV),
+    ]
+    for e in _QUEUED:  # the queue: whole or not at all, then its capacity rules
+        q = dict(lease=0) if e == "read_index" else {}
+        cs += [(e, dict(read_acks=_V), q, _INV), (e, dict(read_acks=_V, read_count=_V), q, _INV),
+               (e, dict(reserved3=1, **_QUEUE), q, _INV), (e, dict(read_cap=3, **_QUEUE), q, _RNG),
+               (e, dict(read_cap=256, **_QUEUE), q, _RNG), (e, dict(read_cap=5, **_QUEUE), q, _INV),
+               (e, dict(read_acks=_V, read_cap=256), q, _INV),
+               (e, dict(reserved3=1, read_cap=256, **_QUEUE), q, _INV)]
+    return cs
+
+
+def test_progress_argument_status_table():
+    """Every entry point that takes a qe_progress: each of its argument rules
+    once, pairs of rules broken at once (the earlier check's status wins), and
+    the empty batch, which is QE_OK only from the point the entry point has
+    reached.  All of it returns before any HIP call."""
+    L = _lib.lib()
+    bad = []
+    for entry, over, other, want in _status_cases():
+        p = None if over is None else _progress(**over)
+        assert want != _OK or p.num_groups == 0, (entry, over)  # nothing may reach a launch
+        got = _ENTRY[entry](L, p, **other)
+        if got != want:
+            bad.append((entry, over, sorted(other), got, want))
+    assert not bad, bad
+    # qe_confchange with a progress: the rules it applies to it
+    cv = {k: _V for k in ["slot_ids", "inc_mask", "out_mask", "learner_mask", "learners_next_mask",
+                          "is_learner", "tracked", "auto_leave"]}
+    ch = _lib.QeConfChanges(op=_V, count=_V, last_index=_V, result=_V)
+    cf = _lib.QeConf(num_groups=4, num_slots=3, **cv)
+    for over in [dict(num_groups=5, stride=5), dict(num_slots=4), dict(stride=3), dict(match=None),
+                 dict(next=None), dict(pending_snapshot=None), dict(peer=None),
+                 dict(num_slots=4, match=None)]:
+        assert L.qe_confchange(C.byref(cf), C.byref(ch), C.byref(_progress(**over)), None) == _INV, over
+    assert L.qe_confchange(C.byref(cf), None, C.byref(_progress()), None) == _INV
+    cf0 = _lib.QeConf(num_groups=0, num_slots=3)
+    assert L.qe_confchange(C.byref(cf0), C.byref(ch), C.byref(_progress(num_slots=4)), None) == _OK
+
+
 def test_comm_argument_errors_without_gpu():
     """qe_comm_* / qe_allreduce_stats validate before touching RCCL."""
     L = _lib.lib()

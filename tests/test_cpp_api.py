@@ -62,3 +62,14 @@ def test_cpp_describe_matches_testdata():
     r = subprocess.run([exe, ROOT], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "PASS: 66 Describe cases" in r.stdout
+
+
+def test_cpp_chunk_plan():
+    """The tiles-per-wave chunk plan every chunked launcher shares
+    (etcd_amd/csrc/qe_launch.hpp), against hand-worked values; host only."""
+    cpp = os.path.join(ROOT, "tests", "cpp")
+    subprocess.check_call(["make", "-s", "-C", cpp, "build/chunk_plan_test"])
+    r = subprocess.run([os.path.join(cpp, "build", "chunk_plan_test")], capture_output=True,
+                       text=True, timeout=60)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "PASS: chunk plan" in r.stdout

@@ -141,7 +141,8 @@ def random_ccs(rng, pool, nmax):
     return out
 
 
-def run_differential(eng, S, pool_size, G, steps, seed, nmax=4):
+def run_differential(eng, S, pool_size, G, steps, seed, nmax=4, trace=None):
+    """`trace`: a list that gets every step's device results and state."""
     rng = random.Random(seed)
     pools = [rng.sample(range(1, 1 << 40), pool_size) for _ in range(G)]
     changers = [cc.Changer() for _ in range(G)]
@@ -162,6 +163,8 @@ def run_differential(eng, S, pool_size, G, steps, seed, nmax=4):
         res = ch.result.cpu().numpy()
         newp = ch.new_progress.cpu().numpy()
         h, hp = cs.host(), ps_host(ps)
+        if trace is not None:
+            trace.append((res, newp, h, hp))
         for g in range(G):
             o = changers[g]
             o.last_index = li
