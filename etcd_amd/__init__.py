@@ -14,5 +14,7 @@ from .tracker import (CommittedBatch, MakeProgressTracker, Progress,  # noqa: F4
                       ProgressTracker, QuorumActiveBatch, TallyVotesBatch)
 from . import confchange  # noqa: F401  (raft/confchange mirror)
 from .engine import Timers, tick  # noqa: F401  (raft.tick() over the resident timers)
+from .engine import (Follower, FollowerOut, LeaderMsgs,  # noqa: F401  (the follower's half)
+                     follower_step)
 
 __version__ = "0.1.0"

@@ -155,6 +155,34 @@ QE_TEV_HEARD, QE_TEV_RESET = 1, 2
 QE_TICK_HUP, QE_TICK_BEAT, QE_TICK_CHECKED_QUORUM, QE_TICK_STEPDOWN = 1, 2, 4, 8
 QE_TICK_TRANSFER_ABORTED = 16
 
+# qe_follower_step
+QE_MAX_MSG_RUNS = 4
+QE_FOLLOW_CHECK_QUORUM, QE_FOLLOW_PREVOTE = 1, 2
+QE_LMSG_NONE, QE_LMSG_APP, QE_LMSG_HEARTBEAT = 0, 1, 2
+QE_FR_NONE, QE_FR_IGNORED, QE_FR_LOWER_TERM_RESP, QE_FR_HEARTBEAT_RESP = 0, 1, 2, 3
+QE_FR_APP_ACCEPT, QE_FR_APP_REJECT, QE_FR_APP_STALE = 4, 5, 6
+QE_FR_REFUSED = 16  # results >= this: nothing of the group changed
+QE_FR_BAD_MSG, QE_FR_COMMIT_PAST_LOG, QE_FR_CONFLICT_COMMITTED, QE_FR_RUNS_FULL = 16, 17, 18, 19
+QE_FR_APP_GAP = 20
+QE_STAT_FOLLOW_APPENDED = 2  # = QE_STAT_COMMIT_SUM
+
+
+class QeFollower(C.Structure):
+    _fields_ = [("term", vp), ("state", vp), ("lead", vp), ("vote", vp), ("flags", u32),
+                ("reserved", u32)]
+
+
+class QeLeaderMsgs(C.Structure):
+    _fields_ = [("type", vp), ("from_", vp), ("term", vp), ("index", vp), ("log_term", vp),
+                ("commit", vp), ("msg_runs", u32), ("reserved", u32), ("ent_len", vp),
+                ("ent_term", vp)]
+
+
+class QeFollowerOut(C.Structure):
+    _fields_ = [("result", vp), ("resp_index", vp), ("reject_hint", vp), ("resp_log_term", vp),
+                ("append_from", vp), ("events", vp)]
+
+
 QE_BL_NONE, QE_BL_LEADER, QE_BL_NOT_MEMBER, QE_BL_RUNS_FULL = 0, 1, 2, 3
 QE_BL_BCAST = 1
 
@@ -250,6 +278,8 @@ PROTOTYPES = {
     "qe_heartbeat": (C.c_int, [C.POINTER(QeProgress), vp, vp, vp, vp]),
     "qe_tick": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeTimers), C.POINTER(QeTickOut), vp,
                           vp]),
+    "qe_follower_step": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeFollower),
+                                   C.POINTER(QeLeaderMsgs), C.POINTER(QeFollowerOut), vp, vp]),
     "qe_switch_config": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeSwitch), vp, vp]),
     "qe_become_leader": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeLeader), vp, vp]),
     "qe_ring_pack": (C.c_int, [u64, u32, u32, u64, vp, vp, vp, vp]),

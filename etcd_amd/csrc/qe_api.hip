@@ -7,6 +7,7 @@
 #include "qe_conf.hpp"
 #include "qe_collect.hpp"
 #include "qe_tick.hpp"
+#include "qe_follow.hpp"
 
 namespace qe {
 
@@ -634,6 +635,61 @@ int qe_tick(const qe_progress *p, const qe_timers *t, const qe_tick_out *out, ui
     return dispatch_tick<s()>(a, p->inc_mask != nullptr, p->out_mask != nullptr,
                               static_cast<hipStream_t>(stream));
   });
+}
+
+int qe_follower_step(const qe_progress *p, const qe_follower *f, const qe_leader_msgs *m,
+                     const qe_follower_out *out, uint64_t *stats, void *stream) {
+  const int rc = check_progress(p);
+  if (rc) return rc;
+  if (!f || !m || !out) return QE_EINVAL;
+  if ((f->flags & ~(QE_FOLLOW_CHECK_QUORUM | QE_FOLLOW_PREVOTE)) || f->reserved || m->reserved)
+    return QE_EINVAL;
+  if (m->msg_runs > QE_MAX_MSG_RUNS || p->log_runs == 0 || p->log_runs > QE_MAX_LOG_RUNS)
+    return QE_EINVAL;
+  if (!f->term || !f->state || !f->lead || !out->result) return QE_EINVAL;
+  if (!m->type || !m->from || !m->term || !m->index || !m->log_term || !m->commit)
+    return QE_EINVAL;
+  if (m->msg_runs && (!m->ent_len || !m->ent_term)) return QE_EINVAL;
+  if (!p->committed || !p->last_index || !p->run_first || !p->run_term || !p->run_count)
+    return QE_EINVAL;
+  if (p->stride < p->num_groups) return QE_EINVAL;
+  if (p->num_groups == 0) return QE_OK;
+  FArgs a{};
+  a.G = p->num_groups;
+  a.goff = p->group_offset;
+  a.stride = p->stride;
+  a.R = p->log_runs;
+  a.E = m->msg_runs;
+  a.S = p->num_slots;
+  a.flags = f->flags;
+  // the log rows are const in qe_progress for the leader's entry points; the
+  // follower appends to them (as qe_propose / qe_become_leader do)
+  a.committed = p->committed;
+  a.last_index = const_cast<uint64_t *>(p->last_index);
+  a.run_first = const_cast<uint64_t *>(p->run_first);
+  a.run_term = const_cast<uint64_t *>(p->run_term);
+  a.run_count = const_cast<uint8_t *>(p->run_count);
+  a.transferee = p->lead_transferee;
+  a.term = f->term;
+  a.state = f->state;
+  a.lead = f->lead;
+  a.vote = f->vote;
+  a.type = m->type;
+  a.from = m->from;
+  a.mterm = m->term;
+  a.index = m->index;
+  a.log_term = m->log_term;
+  a.commit = m->commit;
+  a.ent_len = m->ent_len;
+  a.ent_term = m->ent_term;
+  a.result = out->result;
+  a.resp_index = out->resp_index;
+  a.reject_hint = out->reject_hint;
+  a.resp_log_term = out->resp_log_term;
+  a.append_from = out->append_from;
+  a.events = out->events;
+  a.stats = stats;
+  return dispatch_follow(a, static_cast<hipStream_t>(stream));
 }
 
 int qe_read_index(const qe_progress *p, const uint8_t *request, const uint64_t *key,

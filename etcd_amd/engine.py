@@ -784,6 +784,138 @@ def tick(ps, timers, out=None, stats=None, events=None, ticks=1):
     return out
 
 
+def _load_rows(obj, names, arrays):
+    for k, a in arrays.items():
+        if k not in names:
+            raise KeyError(k)
+        dst = getattr(obj, k)
+        a = np.ascontiguousarray(a)
+        if a.dtype == np.uint64:
+            a = a.view(np.int64)
+        elif a.dtype == np.uint32:
+            a = a.view(np.int32)
+        a = a.reshape(-1)
+        dst[: a.size].copy_(torch.from_numpy(a.copy()).to(dst.device))
+    return obj
+
+
+class Follower:
+    """Device-resident receiver state of G groups (qe_follower): `term` int64
+    storage of r.Term, `state` u8 QE_STATE_* (pass a Timers' `state` tensor to
+    share the row with qe_tick), `lead` and `vote` u8 slots (0xFF = None;
+    vote=False leaves the row out).  check_quorum / prevote are the raft.Config
+    switches that make a lower-term MsgApp / MsgHeartbeat answered."""
+
+    ARRAYS = ("term", "state", "lead", "vote")
+
+    def __init__(self, ps, state=None, vote=True, check_quorum=False, prevote=False):
+        dev, u8 = ps.device, torch.uint8
+        self.term = torch.zeros(ps.G, dtype=torch.int64, device=dev)
+        self.state = state if state is not None else torch.zeros(ps.G, dtype=u8, device=dev)
+        self.lead = torch.full((ps.G,), 0xFF, dtype=u8, device=dev)
+        self.vote = torch.full((ps.G,), 0xFF, dtype=u8, device=dev) if vote else None
+        self.flags = ((_lib.QE_FOLLOW_CHECK_QUORUM if check_quorum else 0) |
+                      (_lib.QE_FOLLOW_PREVOTE if prevote else 0))
+
+    def load_host(self, **arrays):
+        """numpy arrays: term uint64, state / lead / vote uint8."""
+        return _load_rows(self, self.ARRAYS, arrays)
+
+    def struct(self):
+        return _lib.QeFollower(_ptr(self.term), _ptr(self.state), _ptr(self.lead),
+                               _ptr(self.vote), self.flags, 0)
+
+    def host(self):
+        out = {k: (None if getattr(self, k) is None else getattr(self, k).cpu().numpy())
+               for k in self.ARRAYS}
+        out["term"] = out["term"].view(np.uint64)
+        return out
+
+
+class LeaderMsgs:
+    """One MsgApp / MsgHeartbeat per group for qe_follower_step
+    (qe_leader_msgs): type / from_ u8, term / index / log_term / commit int64
+    storage of the u64 fields, and the entries of a MsgApp as msg_runs term
+    runs: ent_len int32 [E][stride], ent_term int64 [E][stride]."""
+
+    ARRAYS = ("type", "from_", "term", "index", "log_term", "commit", "ent_len", "ent_term")
+
+    def __init__(self, ps, msg_runs=1):
+        if not 0 <= int(msg_runs) <= _lib.QE_MAX_MSG_RUNS:
+            raise ValueError("msg_runs must be 0..QE_MAX_MSG_RUNS")
+        dev, i64, u8 = ps.device, torch.int64, torch.uint8
+        self.msg_runs = int(msg_runs)
+        self.type = torch.zeros(ps.G, dtype=u8, device=dev)
+        self.from_ = torch.zeros(ps.G, dtype=u8, device=dev)
+        self.term = torch.zeros(ps.G, dtype=i64, device=dev)
+        self.index = torch.zeros(ps.G, dtype=i64, device=dev)
+        self.log_term = torch.zeros(ps.G, dtype=i64, device=dev)
+        self.commit = torch.zeros(ps.G, dtype=i64, device=dev)
+        n = self.msg_runs * ps.stride
+        self.ent_len = torch.zeros(n, dtype=torch.int32, device=dev) if n else None
+        self.ent_term = torch.zeros(n, dtype=i64, device=dev) if n else None
+
+    def load_host(self, **arrays):
+        """numpy arrays: type / from_ uint8, term / index / log_term / commit /
+        ent_term uint64, ent_len uint32 (`from` is accepted for `from_`)."""
+        if "from" in arrays:
+            arrays["from_"] = arrays.pop("from")
+        if self.msg_runs == 0:
+            arrays = {k: v for k, v in arrays.items() if k not in ("ent_len", "ent_term")}
+        return _load_rows(self, self.ARRAYS, arrays)
+
+    def struct(self):
+        return _lib.QeLeaderMsgs(_ptr(self.type), _ptr(self.from_), _ptr(self.term),
+                                 _ptr(self.index), _ptr(self.log_term), _ptr(self.commit),
+                                 self.msg_runs, 0, _ptr(self.ent_len), _ptr(self.ent_term))
+
+
+class FollowerOut:
+    """Outputs of qe_follower_step (qe_follower_out): `result` u8 QE_FR_*,
+    resp_index / reject_hint / resp_log_term / append_from int64 [G], and
+    `events` u8 QE_TEV_* [G], written for every group, which tick(...,
+    events=) takes as it is."""
+
+    ARRAYS = ("result", "resp_index", "reject_hint", "resp_log_term", "append_from", "events")
+
+    def __init__(self, ps):
+        dev, i64, u8 = ps.device, torch.int64, torch.uint8
+        self.result = torch.zeros(ps.G, dtype=u8, device=dev)
+        self.resp_index = torch.zeros(ps.G, dtype=i64, device=dev)
+        self.reject_hint = torch.zeros(ps.G, dtype=i64, device=dev)
+        self.resp_log_term = torch.zeros(ps.G, dtype=i64, device=dev)
+        self.append_from = torch.zeros(ps.G, dtype=i64, device=dev)
+        self.events = torch.zeros(ps.G, dtype=u8, device=dev)
+
+    def load_host(self, **arrays):
+        """numpy arrays (e.g. sentinels a test wants to see survive)."""
+        return _load_rows(self, self.ARRAYS, arrays)
+
+    def struct(self):
+        return _lib.QeFollowerOut(_ptr(self.result), _ptr(self.resp_index),
+                                  _ptr(self.reject_hint), _ptr(self.resp_log_term),
+                                  _ptr(self.append_from), _ptr(self.events))
+
+    def host(self):
+        out = {k: getattr(self, k).cpu().numpy() for k in self.ARRAYS}
+        for k in ("resp_index", "reject_hint", "resp_log_term", "append_from"):
+            out[k] = out[k].view(np.uint64)
+        return out
+
+
+def follower_step(ps, fol, msgs, out=None, stats=None):
+    """qe_follower_step: one MsgApp / MsgHeartbeat per group through
+    raft.Step's term preamble, handleAppendEntries and handleHeartbeat on the
+    log rows of `ps` (committed, last_index, the term runs) -> FollowerOut."""
+    if out is None:
+        out = FollowerOut(ps)
+    p, f, m, o = ps.struct(), fol.struct(), msgs.struct(), out.struct()
+    check("qe_follower_step",
+          _lib.lib().qe_follower_step(C.byref(p), C.byref(f), C.byref(m), C.byref(o),
+                                      _ptr(stats), _stream(ps.device)))
+    return out
+
+
 class Proposals:
     """One MsgProp per group for qe_propose (qe_proposals, ABI 6):
     num_entries [G] (0 = none), payload [G] (sum of the non-conf-change

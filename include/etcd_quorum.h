@@ -711,6 +711,152 @@ typedef struct qe_tick_out {
 int qe_tick(const qe_progress *p, const qe_timers *t, const qe_tick_out *out,
             uint64_t *stats, void *stream);
 
+/* The follower's half (additive; the ABI version does not change): one
+ * MsgApp or MsgHeartbeat per group stepped through the term preamble of
+ * raft.Step (raft/raft.go:847-920), stepFollower / stepCandidate's arms for
+ * the two messages (:1390-1395, :1433-1440), handleAppendEntries and
+ * handleHeartbeat (:1475-1516) and becomeFollower / reset (:590-619, :686-693)
+ * on the group's log: the term runs of qe_progress, the same rows the group
+ * uses when it leads.  MsgSnap (restore rebuilds the configuration), MsgVote /
+ * MsgPreVote (the lease check needs the election timer) and MsgTimeoutNow stay
+ * with the host.
+ *
+ * Of p it reads num_groups, group_offset, stride, log_runs, num_slots (only to
+ * validate `from`) and reads and WRITES committed, last_index, run_first,
+ * run_term, run_count (declared const in qe_progress for the leader's entry
+ * points; like qe_propose and qe_become_leader this one casts the const away)
+ * and, when non-NULL, lead_transferee (0xFF where becomeFollower runs).  No
+ * other field of p is touched: Progress rows, rings, masks and term_start stay
+ * as they are (the Progress reset of reset() is qe_become_leader's, as for
+ * qe_tick's stepdown).  The log: entries [run_first[0] + 1, last_index],
+ * run_first[0] the dummy (snapshot) index, term(i) = run_term of the highest
+ * run r < run_count with run_first[r] <= i, and 0 outside [run_first[0],
+ * last_index] (raft/log.go:265-285).  The caller keeps raftLog's invariant
+ * run_first[0] <= committed <= last_index, run_first ascending, run_count in
+ * 1..log_runs (results are unspecified otherwise; memory stays in bounds).
+ * Rows r >= run_count[g] are not state: the call may leave or overwrite them.
+ *
+ * Per group, in this order (m = the message, r = the group):
+ *  1. type == QE_LMSG_NONE: result QE_FR_NONE, nothing else of the group is
+ *     read or written (but events[g] = 0, see below).
+ *  2. QE_FR_BAD_MSG (refused): an unknown type, from >= num_slots, and for a
+ *     MsgApp a run with ent_len > 0 and ent_term 0, run terms that decrease
+ *     (over the runs with ent_len > 0), or index + n wrapping.
+ *  3. m.term < r.term (:883-919): with QE_FOLLOW_CHECK_QUORUM or
+ *     QE_FOLLOW_PREVOTE QE_FR_LOWER_TERM_RESP (the empty MsgAppResp of :906),
+ *     else QE_FR_IGNORED.  Nothing changes, no event.
+ *  4. m.term > r.term (:876-877): becomeFollower(m.term, from): term = m.term,
+ *     vote = none (0xFF), state = follower, lead = from, lead_transferee = none,
+ *     event QE_TEV_RESET.
+ *  5. m.term == r.term: a candidate or pre-candidate becomes follower as in 4
+ *     but keeps its vote (reset() clears it only on a term change),
+ *     QE_TEV_RESET; a leader -> QE_FR_IGNORED (stepLeader has no arm for
+ *     these), nothing changes; a follower: lead = from, QE_TEV_HEARD.
+ *  6. MsgHeartbeat: commitTo(m.commit) (never decreases committed); m.commit >
+ *     last_index is the reference's panic (log.go:236-238) ->
+ *     QE_FR_COMMIT_PAST_LOG (refused); else QE_FR_HEARTBEAT_RESP.
+ *  7. MsgApp, entries index+1 .. index+n as term runs (run j: ent_len[j]
+ *     entries of ent_term[j], n = the sum):
+ *     index < committed -> QE_FR_APP_STALE, resp_index = committed (:1476-1479).
+ *     term(index) != log_term -> QE_FR_APP_REJECT: resp_index = index,
+ *       reject_hint = findConflictByTerm(min(index, last_index), log_term)
+ *       (log.go:147-168), resp_log_term = term(reject_hint).
+ *     else lastnewi = index + n and ci = findConflict (log.go:127-138): the
+ *       first entry index whose term differs from the log's (an index past
+ *       last_index differs), 0 when the log holds every entry.
+ *       ci > last_index + 1 (possible only for index > last_index with
+ *       log_term 0, which term() "matches") would leave a hole: the
+ *       reference's slice-bounds panic in truncateAndAppend -> QE_FR_APP_GAP
+ *       (refused).  ci != 0 && ci <= committed: the panic of log.go:94-95 ->
+ *       QE_FR_CONFLICT_COMMITTED (refused).
+ *       ci != 0: last_index = lastnewi; runs with run_first >= ci are dropped
+ *       (kept rows are not rewritten); the pieces of the message's runs from
+ *       ci on are appended in order, a zero-length piece skipped, a piece
+ *       whose term equals the table's last run's term extending that run, any
+ *       other piece a new run starting at its first index; more than log_runs
+ *       rows -> QE_FR_RUNS_FULL (refused: the host compacts and re-delivers,
+ *       as for QE_BL_RUNS_FULL).  ci == 0: the log is not truncated, even
+ *       when it is longer than lastnewi.
+ *       commitTo(min(m.commit, lastnewi)); past last_index (only the index >
+ *       last_index, log_term 0, n = 0 message) -> QE_FR_COMMIT_PAST_LOG.
+ *       QE_FR_APP_ACCEPT, resp_index = lastnewi, append_from = ci.
+ *  8. A refused group (result >= 16): nothing but result is written -- the
+ *     effects of 4 / 5 and the event are dropped too.
+ * Outputs: result[g] for every group.  events[g] (when non-NULL) for every
+ * group too, 0 where no event was raised (NONE, lower term, ignored, refused),
+ * so the array is a complete qe_timers.events for the next qe_tick.  For a
+ * group with 0 < result < 16: resp_index (0 for IGNORED / LOWER_TERM_RESP /
+ * HEARTBEAT_RESP) and append_from (ci of an accept, else 0); reject_hint and
+ * resp_log_term only where result == QE_FR_APP_REJECT.  The heartbeat's
+ * context is not an input: the response echoes it, the host copies it.
+ * stats (over the groups with type != NONE): QE_STAT_GROUPS += 1;
+ * QE_STAT_GRANTED += result == APP_ACCEPT; QE_STAT_REJECTED += result ==
+ * APP_REJECT; QE_STAT_FOLLOW_APPENDED += lastnewi - ci + 1 where ci != 0;
+ * QE_STAT_COMMIT_ADVANCED += committed rose; QE_STAT_INVARIANT_VIOLATIONS +=
+ * result >= 16; QE_STAT_CHECKSUM += h4, h1 = mix64((group_offset + g) *
+ * 0x9E3779B97F4A7C15 ^ 0x2545F4914F6CDD1D ^ result << 56), h2 = mix64(h1 ^
+ * term), h3 = mix64(h2 ^ committed), h4 = mix64(h3 ^ last_index), the values
+ * after the call.
+ * QE_EINVAL: a NULL p / f / m / out / result / term / state / lead / type /
+ * from / m.term / index / log_term / commit / committed / last_index /
+ * run_first / run_term / run_count, msg_runs > QE_MAX_MSG_RUNS, msg_runs > 0
+ * without ent_len / ent_term, log_runs 0 or > QE_MAX_LOG_RUNS, stride <
+ * num_groups, unknown flag bits.  num_groups == 0 is QE_OK. */
+#define QE_MAX_MSG_RUNS 4
+#define QE_FOLLOW_CHECK_QUORUM 1u   /* qe_follower.flags: raft.Config.CheckQuorum */
+#define QE_FOLLOW_PREVOTE 2u        /* raft.Config.PreVote */
+#define QE_LMSG_NONE 0
+#define QE_LMSG_APP 1
+#define QE_LMSG_HEARTBEAT 2
+#define QE_FR_NONE 0
+#define QE_FR_IGNORED 1             /* no response */
+#define QE_FR_LOWER_TERM_RESP 2     /* MsgAppResp{} (:906) */
+#define QE_FR_HEARTBEAT_RESP 3      /* MsgHeartbeatResp */
+#define QE_FR_APP_ACCEPT 4          /* MsgAppResp{Index: resp_index} */
+#define QE_FR_APP_REJECT 5          /* MsgAppResp{Index, Reject, RejectHint, LogTerm} */
+#define QE_FR_APP_STALE 6           /* MsgAppResp{Index: committed} */
+#define QE_FR_REFUSED 16            /* results >= this: nothing of the group changed */
+#define QE_FR_BAD_MSG 16
+#define QE_FR_COMMIT_PAST_LOG 17
+#define QE_FR_CONFLICT_COMMITTED 18
+#define QE_FR_RUNS_FULL 19
+#define QE_FR_APP_GAP 20
+#define QE_STAT_FOLLOW_APPENDED QE_STAT_COMMIT_SUM /* qe_follower_step: entries appended */
+
+typedef struct qe_follower {
+  uint64_t *term;        /* [G] rw r.Term */
+  uint8_t  *state;       /* [G] rw QE_STATE_*, the row qe_timers.state uses */
+  uint8_t  *lead;        /* [G] rw slot of r.lead, >= num_slots = None */
+  uint8_t  *vote;        /* [G] rw or NULL: slot of r.Vote, >= num_slots = None */
+  uint32_t flags;        /* QE_FOLLOW_*; other bits -> QE_EINVAL */
+  uint32_t reserved;
+} qe_follower;
+
+typedef struct qe_leader_msgs {
+  const uint8_t  *type;      /* [G] QE_LMSG_* */
+  const uint8_t  *from;      /* [G] the sender's slot */
+  const uint64_t *term;      /* [G] m.Term */
+  const uint64_t *index;     /* [G] m.Index */
+  const uint64_t *log_term;  /* [G] m.LogTerm */
+  const uint64_t *commit;    /* [G] m.Commit */
+  uint32_t msg_runs;         /* E, 0..QE_MAX_MSG_RUNS */
+  uint32_t reserved;
+  const uint32_t *ent_len;   /* [E][stride] entries of run j */
+  const uint64_t *ent_term;  /* [E][stride] their term */
+} qe_leader_msgs;
+
+typedef struct qe_follower_out {
+  uint8_t  *result;        /* [G] QE_FR_* (required) */
+  uint64_t *resp_index;    /* [G] or NULL */
+  uint64_t *reject_hint;   /* [G] or NULL */
+  uint64_t *resp_log_term; /* [G] or NULL */
+  uint64_t *append_from;   /* [G] or NULL */
+  uint8_t  *events;        /* [G] or NULL: QE_TEV_* */
+} qe_follower_out;
+
+int qe_follower_step(const qe_progress *p, const qe_follower *f, const qe_leader_msgs *m,
+                     const qe_follower_out *out, uint64_t *stats, void *stream);
+
 /* raft.sendAppend / maybeSendAppend(to, send_if_empty) once for the slots of
  * want[g] (raft.go:432-492; bcastAppend after a proposal is want = every
  * tracked slot but the leader's, send_if_empty = 1): paused peers get
