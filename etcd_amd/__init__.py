@@ -16,5 +16,6 @@ from . import confchange  # noqa: F401  (raft/confchange mirror)
 from .engine import Timers, tick  # noqa: F401  (raft.tick() over the resident timers)
 from .engine import (Follower, FollowerOut, LeaderMsgs,  # noqa: F401  (the follower's half)
                      follower_step)
+from .engine import VoteMsgs, VoteOut, Voter, vote_step  # noqa: F401  (elections)
 
 __version__ = "0.1.0"

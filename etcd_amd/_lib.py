@@ -183,6 +183,33 @@ class QeFollowerOut(C.Structure):
                 ("append_from", vp), ("events", vp)]
 
 
+# qe_vote_step
+QE_VMSG_NONE, QE_VMSG_VOTE, QE_VMSG_PREVOTE, QE_VMSG_VOTE_RESP = 0, 1, 2, 3
+QE_VMSG_PREVOTE_RESP, QE_VMSG_HUP, QE_VMSG_TIMEOUT_NOW = 4, 5, 6
+QE_VMF_FORCE, QE_VMF_REJECT = 1, 2
+QE_VOTE_CHECK_QUORUM, QE_VOTE_PREVOTE = 1, 2
+QE_VR_NONE, QE_VR_IGNORED, QE_VR_IN_LEASE, QE_VR_GRANT, QE_VR_REJECT = 0, 1, 2, 3, 4
+QE_VR_STEPPED_DOWN, QE_VR_PENDING, QE_VR_LOST = 5, 6, 7
+QE_VR_CAMPAIGN_PREVOTE, QE_VR_CAMPAIGN_VOTE, QE_VR_WON = 8, 9, 10
+QE_VR_REFUSED = 16  # results >= this: nothing of the group changed
+QE_VR_BAD_MSG = 16
+
+
+class QeVoter(C.Structure):
+    _fields_ = [("timer", vp), ("election_timeout", u32), ("flags", u32), ("voted", vp),
+                ("granted", vp), ("no_campaign", vp)]
+
+
+class QeVoteMsgs(C.Structure):
+    _fields_ = [("type", vp), ("from_", vp), ("term", vp), ("index", vp), ("log_term", vp),
+                ("flags", vp)]
+
+
+class QeVoteOut(C.Structure):
+    _fields_ = [("result", vp), ("resp_term", vp), ("req_log_term", vp), ("req_to", vp),
+                ("elected", vp), ("events", vp)]
+
+
 QE_BL_NONE, QE_BL_LEADER, QE_BL_NOT_MEMBER, QE_BL_RUNS_FULL = 0, 1, 2, 3
 QE_BL_BCAST = 1
 
@@ -280,6 +307,8 @@ PROTOTYPES = {
                           vp]),
     "qe_follower_step": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeFollower),
                                    C.POINTER(QeLeaderMsgs), C.POINTER(QeFollowerOut), vp, vp]),
+    "qe_vote_step": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeFollower), C.POINTER(QeVoter),
+                               C.POINTER(QeVoteMsgs), C.POINTER(QeVoteOut), vp, vp]),
     "qe_switch_config": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeSwitch), vp, vp]),
     "qe_become_leader": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeLeader), vp, vp]),
     "qe_ring_pack": (C.c_int, [u64, u32, u32, u64, vp, vp, vp, vp]),

@@ -8,6 +8,7 @@
 #include "qe_collect.hpp"
 #include "qe_tick.hpp"
 #include "qe_follow.hpp"
+#include "qe_vote.hpp"
 
 namespace qe {
 
@@ -690,6 +691,63 @@ int qe_follower_step(const qe_progress *p, const qe_follower *f, const qe_leader
   a.events = out->events;
   a.stats = stats;
   return dispatch_follow(a, static_cast<hipStream_t>(stream));
+}
+
+int qe_vote_step(const qe_progress *p, const qe_follower *f, const qe_voter *v,
+                 const qe_vote_msgs *m, const qe_vote_out *out, uint64_t *stats, void *stream) {
+  const int rc = check_progress(p);
+  if (rc) return rc;
+  if (!f || !v || !m || !out) return QE_EINVAL;
+  if (v->flags & ~(QE_VOTE_CHECK_QUORUM | QE_VOTE_PREVOTE)) return QE_EINVAL;
+  if ((v->flags & QE_VOTE_CHECK_QUORUM) && !v->timer) return QE_EINVAL;
+  // the saturating 16-bit electionElapsed compares exactly up to here
+  if (v->election_timeout == 0 || v->election_timeout > 32768u) return QE_EINVAL;
+  if (!v->voted != !v->granted) return QE_EINVAL;
+  if (p->out_mask && !p->inc_mask) return QE_EINVAL;
+  if (p->log_runs == 0 || p->log_runs > QE_MAX_LOG_RUNS) return QE_EINVAL;
+  if (!f->term || !f->state || !f->lead || !f->vote || !out->result) return QE_EINVAL;
+  if (!m->type || !m->from || !m->term || !m->index || !m->log_term) return QE_EINVAL;
+  if (!p->last_index || !p->run_first || !p->run_term || !p->run_count) return QE_EINVAL;
+  if (p->stride < p->num_groups) return QE_EINVAL;
+  if (p->num_groups == 0) return QE_OK;
+  VArgs a{};
+  a.G = p->num_groups;
+  a.goff = p->group_offset;
+  a.stride = p->stride;
+  a.R = p->log_runs;
+  a.S = p->num_slots;
+  a.et = v->election_timeout;
+  a.flags = v->flags;
+  a.last_index = p->last_index;
+  a.run_term = p->run_term;
+  a.run_count = p->run_count;
+  a.inc = p->inc_mask;
+  a.out = p->out_mask;
+  a.tracked = p->tracked;
+  a.self_slot = p->self_slot;
+  a.transferee = p->lead_transferee;
+  a.term = f->term;
+  a.state = f->state;
+  a.lead = f->lead;
+  a.vote = f->vote;
+  a.timer = v->timer;
+  a.voted = v->voted;
+  a.granted = v->granted;
+  a.no_campaign = v->no_campaign;
+  a.type = m->type;
+  a.from = m->from;
+  a.mterm = m->term;
+  a.index = m->index;
+  a.log_term = m->log_term;
+  a.mflags = m->flags;
+  a.result = out->result;
+  a.resp_term = out->resp_term;
+  a.req_log_term = out->req_log_term;
+  a.req_to = out->req_to;
+  a.elected = out->elected;
+  a.events = out->events;
+  a.stats = stats;
+  return dispatch_vote(a, static_cast<hipStream_t>(stream));
 }
 
 int qe_read_index(const qe_progress *p, const uint8_t *request, const uint64_t *key,

@@ -916,6 +916,126 @@ def follower_step(ps, fol, msgs, out=None, stats=None):
     return out
 
 
+class Voter:
+    """The election side of G groups (qe_voter): the Votes map as `voted` /
+    `granted` masks [G] (votes=False leaves them out: a voter-only launch,
+    which answers requests and refuses responses and campaigns), `no_campaign`
+    u8 [G] (pass a Timers' row to share it) and `timer`, the Timers' row the
+    lease reads.  Pass `timers` to take timer, no_campaign, election_timeout
+    and check_quorum from it."""
+
+    ARRAYS = ("voted", "granted", "no_campaign")
+
+    def __init__(self, ps, timers=None, votes=True, check_quorum=None, prevote=False,
+                 election_timeout=None, no_campaign=None):
+        dev, md = ps.device, mask_torch_dtype(ps.S)
+        self.timer = timers.timer if timers is not None else None
+        if no_campaign is None and timers is not None:
+            no_campaign = timers.no_campaign
+        self.no_campaign = no_campaign
+        if election_timeout is None:
+            election_timeout = timers.election_timeout if timers is not None else 10
+        self.election_timeout = int(election_timeout)
+        if check_quorum is None:
+            check_quorum = timers.check_quorum if timers is not None else False
+        self.flags = ((_lib.QE_VOTE_CHECK_QUORUM if check_quorum else 0) |
+                      (_lib.QE_VOTE_PREVOTE if prevote else 0))
+        self.voted = torch.zeros(ps.G, dtype=md, device=dev) if votes else None
+        self.granted = torch.zeros(ps.G, dtype=md, device=dev) if votes else None
+
+    def load_host(self, **arrays):
+        """numpy arrays: voted / granted in the mask type, no_campaign uint8."""
+        for k in ("voted", "granted"):
+            if k in arrays and np.asarray(arrays[k]).dtype == np.uint16:
+                arrays[k] = np.ascontiguousarray(arrays[k]).view(np.int16)
+        return _load_rows(self, self.ARRAYS, arrays)
+
+    def struct(self):
+        return _lib.QeVoter(_ptr(self.timer), self.election_timeout, self.flags, _ptr(self.voted),
+                            _ptr(self.granted), _ptr(self.no_campaign))
+
+    def host(self):
+        out = {}
+        for k in ("voted", "granted"):
+            t = getattr(self, k)
+            out[k] = None if t is None else t.cpu().numpy().view(
+                np.uint8 if t.dtype == torch.uint8 else np.uint16)
+        return out
+
+
+class VoteMsgs:
+    """One election message per group for qe_vote_step (qe_vote_msgs): type
+    (QE_VMSG_*) / from_ / flags (QE_VMF_*) u8, term / index / log_term int64
+    storage of the u64 fields."""
+
+    ARRAYS = ("type", "from_", "term", "index", "log_term", "flags")
+
+    def __init__(self, ps):
+        dev, i64, u8 = ps.device, torch.int64, torch.uint8
+        self.type = torch.zeros(ps.G, dtype=u8, device=dev)
+        self.from_ = torch.zeros(ps.G, dtype=u8, device=dev)
+        self.term = torch.zeros(ps.G, dtype=i64, device=dev)
+        self.index = torch.zeros(ps.G, dtype=i64, device=dev)
+        self.log_term = torch.zeros(ps.G, dtype=i64, device=dev)
+        self.flags = torch.zeros(ps.G, dtype=u8, device=dev)
+
+    def load_host(self, **arrays):
+        """numpy arrays: type / from_ / flags uint8, term / index / log_term
+        uint64 (`from` is accepted for `from_`)."""
+        if "from" in arrays:
+            arrays["from_"] = arrays.pop("from")
+        return _load_rows(self, self.ARRAYS, arrays)
+
+    def struct(self):
+        return _lib.QeVoteMsgs(_ptr(self.type), _ptr(self.from_), _ptr(self.term),
+                               _ptr(self.index), _ptr(self.log_term), _ptr(self.flags))
+
+
+class VoteOut:
+    """Outputs of qe_vote_step (qe_vote_out): `result` u8 QE_VR_*, resp_term /
+    req_log_term int64 [G], req_to mask [G], and two rows written for every
+    group: `elected` u8, which Leader(ps, elected=) takes as it is, and
+    `events` u8 QE_TEV_*, which tick(..., events=) takes as it is."""
+
+    ARRAYS = ("result", "resp_term", "req_log_term", "req_to", "elected", "events")
+
+    def __init__(self, ps):
+        dev, i64, u8 = ps.device, torch.int64, torch.uint8
+        self.result = torch.zeros(ps.G, dtype=u8, device=dev)
+        self.resp_term = torch.zeros(ps.G, dtype=i64, device=dev)
+        self.req_log_term = torch.zeros(ps.G, dtype=i64, device=dev)
+        self.req_to = torch.zeros(ps.G, dtype=mask_torch_dtype(ps.S), device=dev)
+        self.elected = torch.zeros(ps.G, dtype=u8, device=dev)
+        self.events = torch.zeros(ps.G, dtype=u8, device=dev)
+
+    def struct(self):
+        return _lib.QeVoteOut(_ptr(self.result), _ptr(self.resp_term), _ptr(self.req_log_term),
+                              _ptr(self.req_to), _ptr(self.elected), _ptr(self.events))
+
+    def host(self):
+        out = {k: getattr(self, k).cpu().numpy() for k in self.ARRAYS}
+        for k in ("resp_term", "req_log_term"):
+            out[k] = out[k].view(np.uint64)
+        if out["req_to"].dtype == np.int16:
+            out["req_to"] = out["req_to"].view(np.uint16)
+        return out
+
+
+def vote_step(ps, fol, voter, msgs, out=None, stats=None):
+    """qe_vote_step: one MsgVote / MsgPreVote / response / MsgHup /
+    MsgTimeoutNow per group through raft.Step's term preamble and lease, the
+    vote decision, the candidate's tally and campaign() on the resident state
+    -> VoteOut.  After a QE_VR_WON: become_leader with Leader(ps,
+    elected=out.elected) and the Follower's term row."""
+    if out is None:
+        out = VoteOut(ps)
+    p, f, v, m, o = ps.struct(), fol.struct(), voter.struct(), msgs.struct(), out.struct()
+    check("qe_vote_step",
+          _lib.lib().qe_vote_step(C.byref(p), C.byref(f), C.byref(v), C.byref(m), C.byref(o),
+                                  _ptr(stats), _stream(ps.device)))
+    return out
+
+
 class Proposals:
     """One MsgProp per group for qe_propose (qe_proposals, ABI 6):
     num_entries [G] (0 = none), payload [G] (sum of the non-conf-change

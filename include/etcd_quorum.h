@@ -717,9 +717,9 @@ int qe_tick(const qe_progress *p, const qe_timers *t, const qe_tick_out *out,
  * the two messages (:1390-1395, :1433-1440), handleAppendEntries and
  * handleHeartbeat (:1475-1516) and becomeFollower / reset (:590-619, :686-693)
  * on the group's log: the term runs of qe_progress, the same rows the group
- * uses when it leads.  MsgSnap (restore rebuilds the configuration), MsgVote /
- * MsgPreVote (the lease check needs the election timer) and MsgTimeoutNow stay
- * with the host.
+ * uses when it leads.  MsgVote / MsgPreVote, their responses and MsgTimeoutNow
+ * are qe_vote_step's (below); MsgSnap (restore rebuilds the configuration)
+ * stays with the host.
  *
  * Of p it reads num_groups, group_offset, stride, log_runs, num_slots (only to
  * validate `from`) and reads and WRITES committed, last_index, run_first,
@@ -856,6 +856,171 @@ typedef struct qe_follower_out {
 
 int qe_follower_step(const qe_progress *p, const qe_follower *f, const qe_leader_msgs *m,
                      const qe_follower_out *out, uint64_t *stats, void *stream);
+
+/* ---- elections: votes, campaigns, tallies (additive in ABI 8) ------------- */
+/* The election between two leaderships on the resident state: one MsgVote /
+ * MsgPreVote / MsgVoteResp / MsgPreVoteResp / MsgHup / MsgTimeoutNow per group
+ * stepped through the term preamble of raft.Step with its lease check
+ * (raft/raft.go:849-920), the vote decision (:930-978), stepCandidate's
+ * response arm (:1399-1414, RecordVote / TallyVotes), hup / campaign (:760-835)
+ * and the header part of becomeFollower / becomePreCandidate / becomeCandidate
+ * / becomeLeader.  The chain: qe_tick raises QE_TICK_HUP -> qe_vote_step (HUP)
+ * campaigns -> the host sends the requests -> qe_vote_step on the voters ->
+ * the host sends the responses -> qe_vote_step on the candidate (WON) ->
+ * qe_become_leader(out->elected, f->term) -> qe_follower_step on the others.
+ * One message per group per call; a host with several messages for one group
+ * makes several calls, in its delivery order.
+ *
+ * f is qe_follower_step's struct; vote is required here, f->flags is not read.
+ * Of p the call reads num_groups, group_offset, stride, num_slots, log_runs,
+ * last_index, run_first, run_term, run_count, inc_mask, out_mask, tracked,
+ * self_slot and writes lead_transferee only (when non-NULL).  The log, the
+ * Progress rows and the rings are never written.  lastTerm = term(last_index)
+ * by the definition above; with the invariant run_first[run_count - 1] <=
+ * last_index, which every reachable log has, it is run_term[run_count - 1],
+ * the only run row the kernel reads.  A slot byte (lead, vote, self_slot)
+ * >= num_slots is None.
+ *
+ * The lease compares electionElapsed (bits 0-15 of the qe_timers.timer row)
+ * with election_timeout: pending events must have been applied first (qe_tick
+ * with ticks == 0).  The saturating 16-bit counter compares exactly because
+ * election_timeout <= 32768.
+ *
+ * Per group, in this order (m = the message, r = the group, S = num_slots):
+ *  1. type == QE_VMSG_NONE: QE_VR_NONE, nothing of the group is read or
+ *     written (events[g] = elected[g] = 0).
+ *  2. QE_VR_BAD_MSG (refused): an unknown type; from >= S or m.term == 0 for
+ *     every type but HUP; a response, HUP or TIMEOUT_NOW when voted, granted or
+ *     p->self_slot is NULL (a voter-only launch); HUP / TIMEOUT_NOW with
+ *     self_slot[g] >= S.
+ *  3. The term preamble (not for HUP, whose term is not read).
+ *     m.term > r.term: inLease = QE_VOTE_CHECK_QUORUM && lead < S &&
+ *       electionElapsed < election_timeout; a request in lease without
+ *       QE_VMF_FORCE -> QE_VR_IN_LEASE, nothing changes.  A PREVOTE, and a
+ *       PREVOTE_RESP without QE_VMF_REJECT, never change the term (:865-872).
+ *       Everything else (VOTE, VOTE_RESP, a rejecting PREVOTE_RESP,
+ *       TIMEOUT_NOW): becomeFollower(m.term, None) -- term = m.term, vote =
+ *       none (0xFF), state = follower, lead = none, lead_transferee = none,
+ *       voted = granted = 0 (when non-NULL), event QE_TEV_RESET ("3d").
+ *     m.term < r.term: a PREVOTE -> QE_VR_REJECT with resp_term = r.term
+ *       (:907-913); anything else -> QE_VR_IGNORED.  Nothing changes.
+ *  4. Requests, in any state (:930-978): canVote = vote == from || (vote ==
+ *     none && lead == none) || (PREVOTE && m.term > r.term); up to date =
+ *     log_term > lastTerm || (log_term == lastTerm && index >= last_index).
+ *     Both -> QE_VR_GRANT, resp_term = m.term; for a VOTE only vote = from and
+ *     QE_TEV_HEARD (electionElapsed = 0, :971) unless RESET was raised.  Else
+ *     QE_VR_REJECT, resp_term = r.term (after 3d).  Learners vote: there is no
+ *     membership check.
+ *  5. Responses (:1399-1414): nothing is done unless the type is the state's
+ *     own (VOTE_RESP <-> candidate, PREVOTE_RESP <-> pre-candidate).  RecordVote:
+ *     the first vote of `from` sticks, its value !QE_VMF_REJECT.  TallyVotes =
+ *     JointConfig.VoteResult over inc_mask / out_mask (NULL inc_mask = every
+ *     slot); a voter outside the masks is recorded, not counted.  Pending ->
+ *     QE_VR_PENDING.  Lost -> becomeFollower(r.term, None): the vote is kept,
+ *     state = follower, lead = lead_transferee = none, voted = granted = 0,
+ *     RESET, QE_VR_LOST.  Won as candidate -> 7; won as pre-candidate -> the
+ *     campaign of 6 as campaignElection.
+ *  6. HUP (hup, :760-781) does nothing on a leader, on a group that is not
+ *     promotable (qe_tick's rule: self_slot < S, in tracked, in inc | out) or
+ *     with no_campaign[g] set.  TIMEOUT_NOW: only a follower (after the
+ *     preamble) goes on, as hup(campaignTransfer); a transfer never pre-votes.
+ *     The campaign (:785-835): HUP under QE_VOTE_PREVOTE -> becomePreCandidate
+ *     (state = pre-candidate, lead = none, voted = granted = the self bit; term,
+ *     vote, lead_transferee and the timers untouched, no event); the tally won
+ *     (a single voter) -> on as an election, else QE_VR_CAMPAIGN_PREVOTE with
+ *     resp_term = r.term + 1.  An election or a transfer -> becomeCandidate
+ *     (term + 1, vote = self, lead = lead_transferee = none, state = candidate,
+ *     voted = granted = the self bit, RESET); the tally won -> 7, else
+ *     QE_VR_CAMPAIGN_VOTE with resp_term = the new term.  Both campaign results
+ *     write req_log_term = lastTerm and req_to = (inc | out) & ~self: the host
+ *     sends Msg{Pre}Vote{Term: resp_term, Index: last_index, LogTerm:
+ *     req_log_term} to req_to and adds the transfer context to a campaign it
+ *     began with TIMEOUT_NOW.
+ *  7. Won (becomeLeader's header part): state = leader, lead = self,
+ *     lead_transferee = none, voted = granted = 0, RESET, elected[g] = 1,
+ *     QE_VR_WON.  The Progress reset, the empty entry and the bcast are
+ *     qe_become_leader's: the host calls it next with out->elected and f->term.
+ *  8. The arm did nothing: QE_VR_STEPPED_DOWN when 3d ran, else QE_VR_IGNORED.
+ *  9. A refused group (result >= 16): nothing but result is written.
+ * Outputs: result, and when non-NULL elected and events, for every group
+ * (elected 1 only where result == WON; events 0 where none was raised): they
+ * are a complete qe_leader.elected and qe_timers.events row.  resp_term only
+ * for GRANT / REJECT / CAMPAIGN_*; req_log_term and req_to only for CAMPAIGN_*.
+ * stats (over the groups with type != NONE): QE_STAT_GROUPS += 1;
+ * QE_STAT_GRANTED += result == GRANT; QE_STAT_REJECTED += result == REJECT;
+ * QE_STAT_VOTE_PENDING += result == PENDING; QE_STAT_ELECTIONS +=
+ * becomeCandidate or becomePreCandidate ran from a hup or TIMEOUT_NOW;
+ * QE_STAT_LEADERS += result == WON; QE_STAT_STEPDOWNS += result == LOST, and
+ * += 3d ran; QE_STAT_INVARIANT_VIOLATIONS += result >= 16; QE_STAT_CHECKSUM
+ * += h4, h1 = mix64((group_offset + g) * 0x9E3779B97F4A7C15 ^
+ * 0x9FB21C651E98DF25 ^ result << 56), h2 = mix64(h1 ^ term), h3 = mix64(h2 ^
+ * (state | lead << 8 | vote << 16 | events << 24)), h4 = mix64(h3 ^ (voted |
+ * granted << 16)), the values after the call, the masks 0 when NULL.
+ * QE_EINVAL: a NULL p / f / v / m / out / result / term / state / lead / vote
+ * / type / from / m.term / index / log_term / last_index / run_term /
+ * run_first / run_count, QE_VOTE_CHECK_QUORUM without timer, election_timeout
+ * outside 1..32768, unknown flag bits, out_mask without inc_mask, exactly one
+ * of voted / granted NULL, log_runs 0 or > QE_MAX_LOG_RUNS, stride <
+ * num_groups.  num_groups == 0 is QE_OK. */
+#define QE_VMSG_NONE 0
+#define QE_VMSG_VOTE 1            /* MsgVote */
+#define QE_VMSG_PREVOTE 2         /* MsgPreVote */
+#define QE_VMSG_VOTE_RESP 3       /* MsgVoteResp */
+#define QE_VMSG_PREVOTE_RESP 4    /* MsgPreVoteResp */
+#define QE_VMSG_HUP 5             /* local MsgHup; the message term is not read */
+#define QE_VMSG_TIMEOUT_NOW 6     /* MsgTimeoutNow */
+#define QE_VMF_FORCE 1u           /* a request: Context == campaignTransfer */
+#define QE_VMF_REJECT 2u          /* a response: m.Reject */
+#define QE_VOTE_CHECK_QUORUM 1u   /* qe_voter.flags: raft.Config.CheckQuorum */
+#define QE_VOTE_PREVOTE 2u        /* raft.Config.PreVote */
+#define QE_VR_NONE 0
+#define QE_VR_IGNORED 1           /* no response */
+#define QE_VR_IN_LEASE 2          /* a request dropped by the lease */
+#define QE_VR_GRANT 3             /* Msg{Pre}VoteResp{Term: resp_term} */
+#define QE_VR_REJECT 4            /* Msg{Pre}VoteResp{Term: resp_term, Reject} */
+#define QE_VR_STEPPED_DOWN 5      /* becomeFollower(m.term, None) and nothing else */
+#define QE_VR_PENDING 6           /* the vote is recorded, the tally is open */
+#define QE_VR_LOST 7
+#define QE_VR_CAMPAIGN_PREVOTE 8  /* send MsgPreVote to req_to */
+#define QE_VR_CAMPAIGN_VOTE 9     /* send MsgVote to req_to */
+#define QE_VR_WON 10              /* call qe_become_leader next */
+#define QE_VR_REFUSED 16          /* results >= this: nothing of the group changed */
+#define QE_VR_BAD_MSG 16
+
+typedef struct qe_voter {
+  const uint32_t *timer;      /* [G] the qe_timers.timer row, read only
+                                 (electionElapsed = bits 0-15); required with
+                                 QE_VOTE_CHECK_QUORUM */
+  uint32_t election_timeout;  /* 1..32768 */
+  uint32_t flags;             /* QE_VOTE_*; other bits -> QE_EINVAL */
+  void *voted, *granted;      /* [G] rw mask-typed or both NULL: the Votes map
+                                 (the rows qe_election_state uses); NULL = a
+                                 voter-only launch */
+  const uint8_t *no_campaign; /* [G] or NULL: non-zero = hup() returns early (a
+                                 pending snapshot or unapplied conf changes,
+                                 raft.go:770-777) */
+} qe_voter;
+
+typedef struct qe_vote_msgs {
+  const uint8_t  *type;      /* [G] QE_VMSG_* */
+  const uint8_t  *from;      /* [G] the sender's slot */
+  const uint64_t *term;      /* [G] m.Term */
+  const uint64_t *index;     /* [G] m.Index (requests) */
+  const uint64_t *log_term;  /* [G] m.LogTerm (requests) */
+  const uint8_t  *flags;     /* [G] QE_VMF_*, or NULL = all 0 */
+} qe_vote_msgs;
+
+typedef struct qe_vote_out {
+  uint8_t  *result;        /* [G] QE_VR_* (required) */
+  uint64_t *resp_term;     /* [G] or NULL */
+  uint64_t *req_log_term;  /* [G] or NULL */
+  void     *req_to;        /* [G] mask-typed or NULL */
+  uint8_t  *elected;       /* [G] or NULL: a complete qe_leader.elected row */
+  uint8_t  *events;        /* [G] or NULL: a complete qe_timers.events row */
+} qe_vote_out;
+
+int qe_vote_step(const qe_progress *p, const qe_follower *f, const qe_voter *v,
+                 const qe_vote_msgs *m, const qe_vote_out *out, uint64_t *stats, void *stream);
 
 /* raft.sendAppend / maybeSendAppend(to, send_if_empty) once for the slots of
  * want[g] (raft.go:432-492; bcastAppend after a proposal is want = every
