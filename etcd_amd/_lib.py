@@ -210,6 +210,36 @@ class QeVoteOut(C.Structure):
                 ("elected", vp), ("events", vp)]
 
 
+# qe_compact
+QE_CP_NONE, QE_CP_CREATED, QE_CP_COMPACTED, QE_CP_SNAP_OUT_OF_DATE, QE_CP_ALREADY = 0, 1, 2, 4, 8
+QE_CP_REFUSED = 16  # results >= this: nothing of the group changed
+QE_CP_OUT_OF_BOUND, QE_CP_PAST_APPLIED = 16, 17
+QE_STAT_COMPACTED = 2  # = QE_STAT_COMMIT_SUM
+
+
+class QeCompaction(C.Structure):
+    _fields_ = [("compact_index", vp), ("create_index", vp), ("applied", vp), ("snap_term", vp),
+                ("result", vp)]
+
+
+# qe_snapshot_step
+QE_SMSG_NONE, QE_SMSG_SNAP = 0, 1
+QE_SR_NONE, QE_SR_IGNORED, QE_SR_STALE, QE_SR_NOT_MEMBER = 0, 1, 2, 3
+QE_SR_FAST_FORWARD, QE_SR_RESTORED = 4, 5
+QE_SR_REFUSED = 16  # results >= this: nothing of the group changed
+QE_SR_BAD_MSG, QE_SR_COMMIT_PAST_LOG, QE_SR_BAD_CONF = 16, 17, 18
+
+
+class QeSnapMsgs(C.Structure):
+    _fields_ = [("type", vp), ("from_", vp), ("term", vp), ("snap_index", vp), ("snap_term", vp),
+                ("cs_inc", vp), ("cs_out", vp), ("cs_learner", vp), ("cs_learners_next", vp),
+                ("cs_auto_leave", vp), ("cs_ids", vp)]
+
+
+class QeSnapOut(C.Structure):
+    _fields_ = [("result", vp), ("resp_index", vp), ("events", vp)]
+
+
 QE_BL_NONE, QE_BL_LEADER, QE_BL_NOT_MEMBER, QE_BL_RUNS_FULL = 0, 1, 2, 3
 QE_BL_BCAST = 1
 
@@ -309,6 +339,10 @@ PROTOTYPES = {
                                    C.POINTER(QeLeaderMsgs), C.POINTER(QeFollowerOut), vp, vp]),
     "qe_vote_step": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeFollower), C.POINTER(QeVoter),
                                C.POINTER(QeVoteMsgs), C.POINTER(QeVoteOut), vp, vp]),
+    "qe_compact": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeCompaction), vp, vp]),
+    "qe_snapshot_step": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeFollower),
+                                   C.POINTER(QeConf), C.POINTER(QeSnapMsgs),
+                                   C.POINTER(QeSnapOut), vp, vp]),
     "qe_switch_config": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeSwitch), vp, vp]),
     "qe_become_leader": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeLeader), vp, vp]),
     "qe_ring_pack": (C.c_int, [u64, u32, u32, u64, vp, vp, vp, vp]),

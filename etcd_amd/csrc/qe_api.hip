@@ -9,6 +9,7 @@
 #include "qe_tick.hpp"
 #include "qe_follow.hpp"
 #include "qe_vote.hpp"
+#include "qe_snap.hpp"
 
 namespace qe {
 
@@ -748,6 +749,106 @@ int qe_vote_step(const qe_progress *p, const qe_follower *f, const qe_voter *v,
   a.events = out->events;
   a.stats = stats;
   return dispatch_vote(a, static_cast<hipStream_t>(stream));
+}
+
+// the term-run log both snapshot entry points work on: the run table with its
+// count, committed and last_index, in rows that hold the batch
+static bool missing_log_model(const qe_progress *p) {
+  return p->log_runs == 0 || p->log_runs > QE_MAX_LOG_RUNS || !p->committed || !p->last_index ||
+         !p->run_first || !p->run_term || !p->run_count || p->stride < p->num_groups;
+}
+
+int qe_compact(const qe_progress *p, const qe_compaction *c, uint64_t *stats, void *stream) {
+  const int rc = check_progress(p);
+  if (rc) return rc;
+  if (!c || !c->compact_index || !c->result) return QE_EINVAL;
+  if (missing_log_model(p)) return QE_EINVAL;
+  if (c->create_index && !p->snap_index) return QE_EINVAL;  // CreateSnapshot records it there
+  if (p->num_groups == 0) return QE_OK;
+  CPArgs a{};
+  a.G = p->num_groups;
+  a.goff = p->group_offset;
+  a.stride = p->stride;
+  a.R = p->log_runs;
+  a.committed = p->committed;
+  a.last_index = p->last_index;
+  // const in qe_progress for the leader's entry points (as in qe_follower_step)
+  a.run_first = const_cast<uint64_t *>(p->run_first);
+  a.run_term = const_cast<uint64_t *>(p->run_term);
+  a.run_count = const_cast<uint8_t *>(p->run_count);
+  a.first_index = const_cast<uint64_t *>(p->first_index);
+  a.snap_index = const_cast<uint64_t *>(p->snap_index);
+  a.compact_index = c->compact_index;
+  a.create_index = c->create_index;
+  a.applied = c->applied;
+  a.snap_term = c->snap_term;
+  a.result = c->result;
+  a.stats = stats;
+  return dispatch_compact(a, static_cast<hipStream_t>(stream));
+}
+
+// the configuration a restore rewrites is the batch's own
+static bool conf_mismatch(const qe_progress *p, const qe_conf *c) {
+  return c->num_groups != p->num_groups || c->num_slots != p->num_slots || c->reserved != 0;
+}
+
+int qe_snapshot_step(const qe_progress *p, const qe_follower *f, const qe_conf *c,
+                     const qe_snap_msgs *m, const qe_snap_out *out, uint64_t *stats,
+                     void *stream) {
+  const int rc = check_progress(p);
+  if (rc) return rc;
+  if (!f || !c || !m || !out) return QE_EINVAL;
+  if (conf_mismatch(p, c)) return QE_EINVAL;
+  if (missing_log_model(p)) return QE_EINVAL;
+  if (!p->self_slot) return QE_EINVAL;  // restore() looks for the receiver in the ConfState
+  if (!f->term || !f->state || !f->lead || !out->result) return QE_EINVAL;
+  if (!m->type || !m->from || !m->term || !m->snap_index || !m->snap_term || !m->cs_inc ||
+      !m->cs_out || !m->cs_learner || !m->cs_learners_next || !m->cs_auto_leave)
+    return QE_EINVAL;
+  if (p->num_groups == 0) return QE_OK;
+  SNArgs a{};
+  a.G = p->num_groups;
+  a.goff = p->group_offset;
+  a.stride = p->stride;
+  a.R = p->log_runs;
+  a.S = p->num_slots;
+  a.committed = p->committed;
+  a.last_index = const_cast<uint64_t *>(p->last_index);
+  a.run_first = const_cast<uint64_t *>(p->run_first);
+  a.run_term = const_cast<uint64_t *>(p->run_term);
+  a.run_count = const_cast<uint8_t *>(p->run_count);
+  a.first_index = const_cast<uint64_t *>(p->first_index);
+  a.snap_index = const_cast<uint64_t *>(p->snap_index);
+  a.self_slot = p->self_slot;
+  a.transferee = p->lead_transferee;
+  a.term = f->term;
+  a.state = f->state;
+  a.lead = f->lead;
+  a.vote = f->vote;
+  a.slot_ids = c->slot_ids;
+  a.c_inc = c->inc_mask;
+  a.c_out = c->out_mask;
+  a.c_lrn = c->learner_mask;
+  a.c_lnx = c->learners_next_mask;
+  a.c_isl = c->is_learner;
+  a.c_trk = c->tracked;
+  a.c_auto = c->auto_leave;
+  a.type = m->type;
+  a.from = m->from;
+  a.mterm = m->term;
+  a.sindex = m->snap_index;
+  a.sterm = m->snap_term;
+  a.m_inc = m->cs_inc;
+  a.m_out = m->cs_out;
+  a.m_lrn = m->cs_learner;
+  a.m_lnx = m->cs_learners_next;
+  a.m_auto = m->cs_auto_leave;
+  a.m_ids = m->cs_ids;
+  a.result = out->result;
+  a.resp_index = out->resp_index;
+  a.events = out->events;
+  a.stats = stats;
+  return dispatch_snap(a, static_cast<hipStream_t>(stream));
 }
 
 int qe_read_index(const qe_progress *p, const uint8_t *request, const uint64_t *key,

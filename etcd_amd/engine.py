@@ -1036,6 +1036,130 @@ def vote_step(ps, fol, voter, msgs, out=None, stats=None):
     return out
 
 
+def _masks_i16(arrays):
+    """uint16 mask rows as the int16 storage the tensors use."""
+    return {k: (np.ascontiguousarray(a).view(np.int16) if np.asarray(a).dtype == np.uint16 else a)
+            for k, a in arrays.items()}
+
+
+class Compaction:
+    """One CreateSnapshot and / or Compact request per group for qe_compact
+    (qe_compaction): compact_index / create_index / applied int64 storage of
+    the u64 rows (0 = no request; create=False / applied=False leave the row
+    out: no snapshot is created, the bound is `committed`), and the outputs
+    snap_term (term(i) where a snapshot was created) and result (QE_CP_*)."""
+
+    ARRAYS = ("compact_index", "create_index", "applied", "snap_term", "result")
+
+    def __init__(self, ps, create=True, applied=True):
+        dev, i64 = ps.device, torch.int64
+        self.compact_index = torch.zeros(ps.G, dtype=i64, device=dev)
+        self.create_index = torch.zeros(ps.G, dtype=i64, device=dev) if create else None
+        self.applied = torch.zeros(ps.G, dtype=i64, device=dev) if applied else None
+        self.snap_term = torch.zeros(ps.G, dtype=i64, device=dev) if create else None
+        self.result = torch.zeros(ps.G, dtype=torch.uint8, device=dev)
+
+    def load_host(self, **arrays):
+        """numpy arrays: the index rows uint64, result uint8."""
+        return _load_rows(self, self.ARRAYS, {k: v for k, v in arrays.items()
+                                              if getattr(self, k) is not None})
+
+    def struct(self):
+        return _lib.QeCompaction(_ptr(self.compact_index), _ptr(self.create_index),
+                                 _ptr(self.applied), _ptr(self.snap_term), _ptr(self.result))
+
+    def host(self):
+        out = {k: (None if getattr(self, k) is None else getattr(self, k).cpu().numpy())
+               for k in self.ARRAYS}
+        for k in self.ARRAYS[:4]:
+            if out[k] is not None:
+                out[k] = out[k].view(np.uint64)
+        return out
+
+
+def compact(ps, cp, stats=None):
+    """qe_compact: MemoryStorage.CreateSnapshot / Compact on the term runs of
+    `ps` (run_first / run_term / run_count, first_index, snap_index), bounded
+    by min(applied, committed) -> the Compaction with result / snap_term."""
+    p, c = ps.struct(), cp.struct()
+    check("qe_compact", _lib.lib().qe_compact(C.byref(p), C.byref(c), _ptr(stats),
+                                              _stream(ps.device)))
+    return cp
+
+
+class SnapMsgs:
+    """One MsgSnap per group for qe_snapshot_step (qe_snap_msgs): type / from_
+    u8, term / snap_index / snap_term int64 storage of the u64 fields, the
+    ConfState as slot masks in the receiver's numbering (cs_inc, cs_out,
+    cs_learner, cs_learners_next), cs_auto_leave u8 and, with ids=True, cs_ids
+    [S][stride] (the peer id of each slot)."""
+
+    MASKS = ("cs_inc", "cs_out", "cs_learner", "cs_learners_next")
+    ARRAYS = ("type", "from_", "term", "snap_index", "snap_term") + MASKS + ("cs_auto_leave",
+                                                                             "cs_ids")
+
+    def __init__(self, ps, ids=False):
+        dev, i64, u8 = ps.device, torch.int64, torch.uint8
+        self.type = torch.zeros(ps.G, dtype=u8, device=dev)
+        self.from_ = torch.zeros(ps.G, dtype=u8, device=dev)
+        self.term = torch.zeros(ps.G, dtype=i64, device=dev)
+        self.snap_index = torch.zeros(ps.G, dtype=i64, device=dev)
+        self.snap_term = torch.zeros(ps.G, dtype=i64, device=dev)
+        for k in self.MASKS:
+            setattr(self, k, torch.zeros(ps.G, dtype=mask_torch_dtype(ps.S), device=dev))
+        self.cs_auto_leave = torch.zeros(ps.G, dtype=u8, device=dev)
+        self.cs_ids = torch.zeros(ps.S * ps.stride, dtype=i64, device=dev) if ids else None
+
+    def load_host(self, **arrays):
+        """numpy arrays: u8 rows uint8, u64 rows uint64, masks uint8 / uint16
+        (`from` is accepted for `from_`)."""
+        if "from" in arrays:
+            arrays["from_"] = arrays.pop("from")
+        if self.cs_ids is None:
+            arrays.pop("cs_ids", None)
+        return _load_rows(self, self.ARRAYS, _masks_i16(arrays))
+
+    def struct(self):
+        return _lib.QeSnapMsgs(*[_ptr(getattr(self, k)) for k in self.ARRAYS])
+
+
+class SnapOut:
+    """Outputs of qe_snapshot_step (qe_snap_out): result u8 QE_SR_*,
+    resp_index int64 [G] (the MsgAppResp's index where one goes out) and events
+    u8 QE_TEV_* [G], written for every group."""
+
+    ARRAYS = ("result", "resp_index", "events")
+
+    def __init__(self, ps):
+        dev = ps.device
+        self.result = torch.zeros(ps.G, dtype=torch.uint8, device=dev)
+        self.resp_index = torch.zeros(ps.G, dtype=torch.int64, device=dev)
+        self.events = torch.zeros(ps.G, dtype=torch.uint8, device=dev)
+
+    def struct(self):
+        return _lib.QeSnapOut(_ptr(self.result), _ptr(self.resp_index), _ptr(self.events))
+
+    def host(self):
+        out = {k: getattr(self, k).cpu().numpy() for k in self.ARRAYS}
+        out["resp_index"] = out["resp_index"].view(np.uint64)
+        return out
+
+
+def snapshot_step(ps, fol, conf, msgs, out=None, stats=None):
+    """qe_snapshot_step: one MsgSnap per group through raft.Step's term
+    preamble and handleSnapshot / restore on the log rows of `ps` and the
+    configuration rows of `conf` (a ConfState; point its inc / out / tracked at
+    the tensors of `ps` to restore the rows qe_vote_step and qe_tick read; a row
+    set to None is not written) -> SnapOut."""
+    if out is None:
+        out = SnapOut(ps)
+    p, f, c, m, o = ps.struct(), fol.struct(), conf.struct(), msgs.struct(), out.struct()
+    check("qe_snapshot_step",
+          _lib.lib().qe_snapshot_step(C.byref(p), C.byref(f), C.byref(c), C.byref(m),
+                                      C.byref(o), _ptr(stats), _stream(ps.device)))
+    return out
+
+
 class Proposals:
     """One MsgProp per group for qe_propose (qe_proposals, ABI 6):
     num_entries [G] (0 = none), payload [G] (sum of the non-conf-change

@@ -718,8 +718,8 @@ int qe_tick(const qe_progress *p, const qe_timers *t, const qe_tick_out *out,
  * handleHeartbeat (:1475-1516) and becomeFollower / reset (:590-619, :686-693)
  * on the group's log: the term runs of qe_progress, the same rows the group
  * uses when it leads.  MsgVote / MsgPreVote, their responses and MsgTimeoutNow
- * are qe_vote_step's (below); MsgSnap (restore rebuilds the configuration)
- * stays with the host.
+ * are qe_vote_step's (below); MsgSnap (restore rebuilds the configuration) is
+ * qe_snapshot_step's (further below).
  *
  * Of p it reads num_groups, group_offset, stride, log_runs, num_slots (only to
  * validate `from`) and reads and WRITES committed, last_index, run_first,
@@ -774,8 +774,9 @@ int qe_tick(const qe_progress *p, const qe_timers *t, const qe_tick_out *out,
  *       ci on are appended in order, a zero-length piece skipped, a piece
  *       whose term equals the table's last run's term extending that run, any
  *       other piece a new run starting at its first index; more than log_runs
- *       rows -> QE_FR_RUNS_FULL (refused: the host compacts and re-delivers,
- *       as for QE_BL_RUNS_FULL).  ci == 0: the log is not truncated, even
+ *       rows -> QE_FR_RUNS_FULL (refused: qe_compact drops the runs below the
+ *       applied index on the device and the host re-delivers, as for
+ *       QE_BL_RUNS_FULL).  ci == 0: the log is not truncated, even
  *       when it is longer than lastnewi.
  *       commitTo(min(m.commit, lastnewi)); past last_index (only the index >
  *       last_index, log_term 0, n = 0 message) -> QE_FR_COMMIT_PAST_LOG.
@@ -1127,8 +1128,8 @@ int qe_propose(const qe_progress *p, const qe_proposals *prop, uint64_t *stats, 
                                panic (a candidate is promotable, so a voter);
                                nothing changes                               */
 #define QE_BL_RUNS_FULL 3   /* the new term's run does not fit the log model's
-                               log_runs: nothing changes (the host compacts
-                               the run table and retries)                    */
+                               log_runs: nothing changes (qe_compact frees
+                               rows on the device, then retry)               */
 #define QE_BL_BCAST 1u      /* qe_leader.flags: then bcastAppend, as
                                stepCandidate does after winning (raft.go:
                                1405-1407)                                     */
@@ -1428,6 +1429,170 @@ typedef struct qe_conf_changes {
  * Inflights, no pending snapshot. */
 int qe_confchange(const qe_conf *c, const qe_conf_changes *ch, const qe_progress *p,
                   void *stream);
+
+/* ---- snapshots: the log's lower end (additive in ABI 8) ------------------- */
+/* qe_compact: MemoryStorage.CreateSnapshot and MemoryStorage.Compact
+ * (raft/storage.go:194-236) on the term-run log of p, per group create then
+ * compact, as etcd's server does it.  Of p it reads num_groups, group_offset,
+ * stride, log_runs, committed, last_index and reads and WRITES run_first,
+ * run_term, run_count and, when non-NULL, first_index and snap_index (declared
+ * const in qe_progress; cast away as qe_follower_step does).  committed,
+ * last_index, term_start, the Progress rows and the rings are never touched: a
+ * leader's next send sees Next < firstIndex by itself.
+ *   bound = min(applied[g], committed[g]), committed[g] with no applied row.
+ *     The reference leaves "not past applied" to the application
+ *     (storage.go:215-217); the engine enforces it, which also keeps
+ *     run_first[0] <= committed.
+ *   Create, i = create_index[g] != 0 (storage.go:194-213):
+ *     i <= snap_index[g] -> bit QE_CP_SNAP_OUT_OF_DATE (ErrSnapOutOfDate :197-199),
+ *       nothing changes for this operation;
+ *     else i > last_index (the panic of :202-204) or i < run_first[0] (the
+ *       slice index of :207 below zero) -> QE_CP_OUT_OF_BOUND (refused);
+ *     else i > bound -> QE_CP_PAST_APPLIED (refused);
+ *     else snap_index[g] = i, snap_term[g] = term(i) (:206-207), bit
+ *       QE_CP_CREATED.
+ *   Compact, ci = compact_index[g] != 0 (storage.go:218-236):
+ *     ci <= run_first[0] -> bit QE_CP_ALREADY (ErrCompacted :222-224), nothing
+ *       changes;
+ *     ci > last_index (the panic of :225-227) -> QE_CP_OUT_OF_BOUND (refused);
+ *     ci > bound -> QE_CP_PAST_APPLIED (refused);
+ *     else with r* the highest run below run_count with run_first[r*] <= ci
+ *       (:229-234): row 0 becomes (ci, run_term[r*]), row k >= 1 becomes the old
+ *       row r* + k, run_count -= r*, first_index[g] = ci + 1, bit
+ *       QE_CP_COMPACTED.  With r* == 0 only run_first[0] is stored: a kept row
+ *       is never rewritten (the contract of qe_follower_step).  Rows >= the new
+ *       run_count are not state and keep their bytes.
+ *   A result >= QE_CP_REFUSED: nothing of the group changed, the effects of the
+ *   other operation included; where both operations refuse, the create's code
+ *   stands.  The bits below 16 combine.
+ * result[g] is written for every group (QE_CP_NONE without a request).
+ * stats (over the groups with a request): QE_STAT_GROUPS += 1;
+ * QE_STAT_COMPACTED += ci - the old run_first[0] where compacted;
+ * QE_STAT_INVARIANT_VIOLATIONS += result >= 16; QE_STAT_CHECKSUM += h4, h1 =
+ * mix64((group_offset + g) * 0x9E3779B97F4A7C15 ^ 0xD1B54A32D192ED03 ^ result
+ * << 56), h2 = mix64(h1 ^ run_first[0]), h3 = mix64(h2 ^ run_count), h4 =
+ * mix64(h3 ^ snap_index) (0 without the row), the values after the call.
+ * QE_EINVAL: a NULL p / c / compact_index / result / committed / last_index /
+ * run_first / run_term / run_count, create_index given with p->snap_index NULL,
+ * log_runs 0 or > QE_MAX_LOG_RUNS, stride < num_groups.  num_groups == 0 is
+ * QE_OK. */
+#define QE_CP_NONE 0
+#define QE_CP_CREATED 1u            /* snap_index / snap_term written */
+#define QE_CP_COMPACTED 2u          /* the dummy row moved to compact_index */
+#define QE_CP_SNAP_OUT_OF_DATE 4u   /* ErrSnapOutOfDate */
+#define QE_CP_ALREADY 8u            /* ErrCompacted */
+#define QE_CP_REFUSED 16            /* results >= this: nothing of the group changed */
+#define QE_CP_OUT_OF_BOUND 16
+#define QE_CP_PAST_APPLIED 17
+#define QE_STAT_COMPACTED QE_STAT_COMMIT_SUM /* qe_compact: entries compacted */
+
+typedef struct qe_compaction {
+  const uint64_t *compact_index; /* [G] Compact(ci); 0 = none                */
+  const uint64_t *create_index;  /* [G] or NULL; CreateSnapshot(i); 0 = none */
+  const uint64_t *applied;       /* [G] or NULL                              */
+  uint64_t *snap_term;           /* [G] out or NULL: term(i) where created   */
+  uint8_t  *result;              /* [G] out, required                        */
+} qe_compaction;
+
+int qe_compact(const qe_progress *p, const qe_compaction *c, uint64_t *stats, void *stream);
+
+/* qe_snapshot_step: one MsgSnap per group stepped through the term preamble of
+ * raft.Step (raft/raft.go:849-920), the MsgSnap arms of stepFollower /
+ * stepCandidate (:1396-1398, :1441-1444) and handleSnapshot / restore
+ * (:1518-1614) with raftLog.restore (raft/log.go:333-337) and
+ * confchange.Restore (raft/confchange/restore.go:21-155).
+ *
+ * p is the receiver's log as in qe_follower_step, plus first_index and
+ * snap_index (written when non-NULL) and self_slot (required).  c is the
+ * group's tracker.Config in slot form with DEVICE pointers; its inc_mask,
+ * out_mask and tracked rows are normally the very buffers p points at (the
+ * rows qe_vote_step and qe_tick read).  The ConfState of the message comes in
+ * the RECEIVER's slot numbering: slot assignment stays with the host, and a
+ * peer present before and after the restore keeps its slot.  The engine cannot
+ * check this.
+ *
+ * Per group, in this order (m = the message, r = the group):
+ *  1. type == QE_SMSG_NONE: QE_SR_NONE, nothing else of the group is read or
+ *     written (but events[g] = 0).
+ *  2. QE_SR_BAD_MSG (refused): an unknown type or from >= num_slots.
+ *  3. The preamble, as steps 3-5 of qe_follower_step, except that m.term <
+ *     r.term is ALWAYS QE_SR_IGNORED, whatever CheckQuorum and PreVote say:
+ *     :884 lists only MsgApp and MsgHeartbeat (so qe_follower's flags are not
+ *     read).  m.term > r.term: becomeFollower(m.term, from), QE_TEV_RESET.
+ *     Equal terms: a candidate or pre-candidate becomes follower and keeps its
+ *     vote (:1396-1398), QE_TEV_RESET; a leader -> QE_SR_IGNORED (stepLeader
+ *     has no MsgSnap arm), nothing changes; a follower: lead = from,
+ *     QE_TEV_HEARD (:1441-1444).
+ *  4. sindex <= committed (:1535-1537) -> QE_SR_STALE, resp_index = committed.
+ *  5. The self bit is not in cs_inc | cs_learner | cs_out, or self_slot >=
+ *     num_slots (:1554-1580) -> QE_SR_NOT_MEMBER, resp_index = committed.
+ *  6. term(sindex) == sterm by the run table (matchTerm, :1584-1589):
+ *     commitTo(sindex), QE_SR_FAST_FORWARD, resp_index = sindex.  term() is 0
+ *     outside the log, so sterm == 0 with sindex > last_index "matches" and
+ *     would commit past the log (the panic of log.go:236-238) ->
+ *     QE_SR_COMMIT_PAST_LOG (refused), as QE_FR_APP_GAP's case.
+ *  7. A ConfState confchange.Restore fails on, or whose result is not
+ *     equivalent to it (assertConfStatesEquivalent), is the reference's panic
+ *     (:1600-1606) -> QE_SR_BAD_CONF (refused).  In mask form: cs_inc == 0
+ *     with cs_out | cs_learner != 0 (the all-empty ConfState restores to the
+ *     empty configuration without error, but step 5 answers it first);
+ *     (cs_inc | cs_out) & cs_learner != 0; cs_learners_next not a subset of
+ *     cs_out & ~cs_inc; cs_out == 0 with cs_learners_next != 0 or
+ *     cs_auto_leave set; a bit at or past num_slots in any of the four.
+ *  8. Restore -> QE_SR_RESTORED, resp_index = sindex: committed = last_index =
+ *     sindex; the run table is the single row (sindex, sterm), run_count 1;
+ *     first_index = sindex + 1 and snap_index = sindex where those rows are
+ *     non-NULL; every non-NULL row of c is written for the group: the four
+ *     masks, is_learner = cs_learner, tracked = cs_inc | cs_out | cs_learner,
+ *     auto_leave (0 / 1) and, with cs_ids and slot_ids, the id of each tracked
+ *     slot and 0 for an untracked one.  The Progress rows and the rings are
+ *     not written (as in qe_follower_step: reset() in qe_become_leader
+ *     rewrites them before anything reads them).  The host sets no_campaign[g]
+ *     until it has applied the snapshot (hasPendingSnapshot in promotable, :1618-1621).
+ *  9. A refused group (result >= 16): nothing but result is written -- the
+ *     effects of 3 and the event are dropped too.
+ * Outputs: result[g] and events[g] (when non-NULL) for every group, events 0
+ * where none was raised, so the array is a complete qe_timers.events row.
+ * resp_index only where a MsgAppResp goes out: STALE, NOT_MEMBER,
+ * FAST_FORWARD, RESTORED.
+ * stats (over the groups with type != NONE): QE_STAT_GROUPS += 1;
+ * QE_STAT_GRANTED += RESTORED; QE_STAT_REJECTED += STALE or NOT_MEMBER;
+ * QE_STAT_COMMIT_ADVANCED += committed rose; QE_STAT_INVARIANT_VIOLATIONS +=
+ * result >= 16; QE_STAT_CHECKSUM += h4 of qe_follower_step's chain (result,
+ * term, committed, last_index after the call) with the constant
+ * 0x8CB92BA72F3D8DD7.
+ * QE_EINVAL: a NULL p / f / c / m / out / result / term / state / lead / type /
+ * from / m.term / snap_index / snap_term / cs_inc / cs_out / cs_learner /
+ * cs_learners_next / cs_auto_leave / committed / last_index / run_first /
+ * run_term / run_count / self_slot, c->num_groups or c->num_slots other than
+ * p's, c->reserved, stride < num_groups, log_runs 0 or > QE_MAX_LOG_RUNS.
+ * num_groups == 0 is QE_OK. */
+#define QE_SMSG_NONE 0
+#define QE_SMSG_SNAP 1
+#define QE_SR_NONE 0
+#define QE_SR_IGNORED 1             /* no response */
+#define QE_SR_STALE 2               /* MsgAppResp{Index: committed} */
+#define QE_SR_NOT_MEMBER 3          /* MsgAppResp{Index: committed} */
+#define QE_SR_FAST_FORWARD 4        /* MsgAppResp{Index: committed} after commitTo */
+#define QE_SR_RESTORED 5            /* MsgAppResp{Index: lastIndex} */
+#define QE_SR_REFUSED 16            /* results >= this: nothing of the group changed */
+#define QE_SR_BAD_MSG 16
+#define QE_SR_COMMIT_PAST_LOG 17
+#define QE_SR_BAD_CONF 18
+
+typedef struct qe_snap_msgs {
+  const uint8_t  *type;        /* [G] 0 = none, 1 = MsgSnap */
+  const uint8_t  *from;        /* [G] sender's slot */
+  const uint64_t *term;        /* [G] m.Term */
+  const uint64_t *snap_index, *snap_term;              /* [G] Metadata.Index / Term */
+  const void *cs_inc, *cs_out, *cs_learner, *cs_learners_next; /* [G] mask-typed ConfState,
+                                  in the RECEIVER's slot numbering */
+  const uint8_t  *cs_auto_leave;  /* [G] */
+  const uint64_t *cs_ids;         /* [S][stride] or NULL: peer id per slot */
+} qe_snap_msgs;
+typedef struct qe_snap_out { uint8_t *result; uint64_t *resp_index; uint8_t *events; } qe_snap_out;
+int qe_snapshot_step(const qe_progress *p, const qe_follower *f, const qe_conf *c,
+                     const qe_snap_msgs *m, const qe_snap_out *out, uint64_t *stats, void *stream);
 
 /* ---- Ready deltas ------------------------------------------------------ */
 
