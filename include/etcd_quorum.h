@@ -528,7 +528,16 @@ typedef struct qe_peer_msgs {
  * A send is raft.maybeSendAppend (raft.go:432-492) on the log model; see
  * qe_progress_send.  Messages from untracked slots are dropped.  An accept
  * with index > lastIndex is processed as the reference does and counted as
- * an invariant violation. */
+ * an invariant violation.
+ * qe_peer_msgs carries no term: raft.Step's preamble (raft.go:849-920) for
+ * these messages is the HOST's.  Only a response of the group's own term,
+ * received while the group leads, belongs here; a lower term is dropped, a
+ * group that does not lead has no arm for it, and a higher term goes to
+ * qe_vote_step as a QE_VMSG_VOTE_RESP of that term with QE_VMF_REJECT
+ * (becomeFollower(m.Term, None), QE_VR_STEPPED_DOWN: the same transition for
+ * every response type).  MsgSnapStatus is local (term 0, node.ReportSnapshot):
+ * the host's transport reports every MsgSnap it carried, or a peer whose
+ * MsgSnap was lost stays in StateSnapshot. */
 int qe_progress_step(const qe_progress *p, const qe_peer_msgs *m, uint64_t *stats,
                      void *stream);
 
@@ -637,7 +646,12 @@ int qe_heartbeat(const qe_progress *p, uint64_t *commit, uint32_t *ctx, void *se
  *       qe_check_quorum): QE_TICK_CHECKED_QUORUM, quorum_active[g] written;
  *       not active -> becomeFollower(r.Term, None): state = follower, both
  *       counters 0, the timeout drawn again, lead_transferee = none,
- *       QE_TICK_STEPDOWN.  The peer words are left as qe_check_quorum leaves
+ *       QE_TICK_STEPDOWN.  r.lead = None of that becomeFollower is the HOST's:
+ *       qe_tick has no access to qe_follower.lead, so the host stores 0xFF
+ *       there before the group's next qe_vote_step (a stale lead keeps the
+ *       lease of raft.go:853-863 closed and canVote false).  The Votes masks
+ *       need nothing: qe_vote_step clears them on the next campaign or term
+ *       change.  The peer words are left as qe_check_quorum leaves
  *       them: the wholesale Progress reset of reset() (:600-616) is
  *       qe_become_leader's, the next time the group leads;
  *       still leader with lead_transferee[g] < S -> abortLeaderTransfer
