@@ -80,6 +80,17 @@ __global__ void k_stats_reduce(const uint64_t *stats, uint64_t *out) {
 // ===========================================================================
 using namespace qe;
 
+// The head the argument struct of every step kernel (qe_follower_step, qe_vote_step,
+// qe_snapshot_step, qe_compact) starts with, and the statistics.
+template <class A>
+static void step_head(const qe_progress *p, uint64_t *stats, A &a) {
+  a.G = p->num_groups;
+  a.goff = p->group_offset;
+  a.stride = p->stride;
+  a.R = p->log_runs;
+  a.stats = stats;
+}
+
 extern "C" {
 
 int qe_abi_version(void) { return QE_ABI_VERSION; }
@@ -639,6 +650,20 @@ int qe_tick(const qe_progress *p, const qe_timers *t, const qe_tick_out *out, ui
   });
 }
 
+// What the step entry points (qe_follower_step, qe_vote_step, qe_snapshot_step,
+// qe_compact) ask of their arguments alike.  The term-run log model: the run
+// table with its count and last_index, and committed for all but the vote,
+// in rows that hold the batch.
+static bool missing_log_model(const qe_progress *p, bool committed = true) {
+  return p->log_runs == 0 || p->log_runs > QE_MAX_LOG_RUNS || (committed && !p->committed) ||
+         !p->last_index || !p->run_first || !p->run_term || !p->run_count ||
+         p->stride < p->num_groups;
+}
+// The qe_follower header rows; `vote` is optional except to qe_vote_step.
+static bool missing_follower(const qe_follower *f, bool vote = false) {
+  return !f->term || !f->state || !f->lead || (vote && !f->vote);
+}
+
 int qe_follower_step(const qe_progress *p, const qe_follower *f, const qe_leader_msgs *m,
                      const qe_follower_out *out, uint64_t *stats, void *stream) {
   const int rc = check_progress(p);
@@ -646,21 +671,14 @@ int qe_follower_step(const qe_progress *p, const qe_follower *f, const qe_leader
   if (!f || !m || !out) return QE_EINVAL;
   if ((f->flags & ~(QE_FOLLOW_CHECK_QUORUM | QE_FOLLOW_PREVOTE)) || f->reserved || m->reserved)
     return QE_EINVAL;
-  if (m->msg_runs > QE_MAX_MSG_RUNS || p->log_runs == 0 || p->log_runs > QE_MAX_LOG_RUNS)
-    return QE_EINVAL;
-  if (!f->term || !f->state || !f->lead || !out->result) return QE_EINVAL;
+  if (m->msg_runs > QE_MAX_MSG_RUNS || missing_log_model(p)) return QE_EINVAL;
+  if (missing_follower(f) || !out->result) return QE_EINVAL;
   if (!m->type || !m->from || !m->term || !m->index || !m->log_term || !m->commit)
     return QE_EINVAL;
   if (m->msg_runs && (!m->ent_len || !m->ent_term)) return QE_EINVAL;
-  if (!p->committed || !p->last_index || !p->run_first || !p->run_term || !p->run_count)
-    return QE_EINVAL;
-  if (p->stride < p->num_groups) return QE_EINVAL;
   if (p->num_groups == 0) return QE_OK;
   FArgs a{};
-  a.G = p->num_groups;
-  a.goff = p->group_offset;
-  a.stride = p->stride;
-  a.R = p->log_runs;
+  step_head(p, stats, a);
   a.E = m->msg_runs;
   a.S = p->num_slots;
   a.flags = f->flags;
@@ -690,7 +708,6 @@ int qe_follower_step(const qe_progress *p, const qe_follower *f, const qe_leader
   a.resp_log_term = out->resp_log_term;
   a.append_from = out->append_from;
   a.events = out->events;
-  a.stats = stats;
   return dispatch_follow(a, static_cast<hipStream_t>(stream));
 }
 
@@ -705,17 +722,12 @@ int qe_vote_step(const qe_progress *p, const qe_follower *f, const qe_voter *v,
   if (v->election_timeout == 0 || v->election_timeout > 32768u) return QE_EINVAL;
   if (!v->voted != !v->granted) return QE_EINVAL;
   if (p->out_mask && !p->inc_mask) return QE_EINVAL;
-  if (p->log_runs == 0 || p->log_runs > QE_MAX_LOG_RUNS) return QE_EINVAL;
-  if (!f->term || !f->state || !f->lead || !f->vote || !out->result) return QE_EINVAL;
+  if (missing_log_model(p, false)) return QE_EINVAL;
+  if (missing_follower(f, true) || !out->result) return QE_EINVAL;
   if (!m->type || !m->from || !m->term || !m->index || !m->log_term) return QE_EINVAL;
-  if (!p->last_index || !p->run_first || !p->run_term || !p->run_count) return QE_EINVAL;
-  if (p->stride < p->num_groups) return QE_EINVAL;
   if (p->num_groups == 0) return QE_OK;
   VArgs a{};
-  a.G = p->num_groups;
-  a.goff = p->group_offset;
-  a.stride = p->stride;
-  a.R = p->log_runs;
+  step_head(p, stats, a);
   a.S = p->num_slots;
   a.et = v->election_timeout;
   a.flags = v->flags;
@@ -747,15 +759,7 @@ int qe_vote_step(const qe_progress *p, const qe_follower *f, const qe_voter *v,
   a.req_to = out->req_to;
   a.elected = out->elected;
   a.events = out->events;
-  a.stats = stats;
   return dispatch_vote(a, static_cast<hipStream_t>(stream));
-}
-
-// the term-run log both snapshot entry points work on: the run table with its
-// count, committed and last_index, in rows that hold the batch
-static bool missing_log_model(const qe_progress *p) {
-  return p->log_runs == 0 || p->log_runs > QE_MAX_LOG_RUNS || !p->committed || !p->last_index ||
-         !p->run_first || !p->run_term || !p->run_count || p->stride < p->num_groups;
 }
 
 int qe_compact(const qe_progress *p, const qe_compaction *c, uint64_t *stats, void *stream) {
@@ -766,10 +770,7 @@ int qe_compact(const qe_progress *p, const qe_compaction *c, uint64_t *stats, vo
   if (c->create_index && !p->snap_index) return QE_EINVAL;  // CreateSnapshot records it there
   if (p->num_groups == 0) return QE_OK;
   CPArgs a{};
-  a.G = p->num_groups;
-  a.goff = p->group_offset;
-  a.stride = p->stride;
-  a.R = p->log_runs;
+  step_head(p, stats, a);
   a.committed = p->committed;
   a.last_index = p->last_index;
   // const in qe_progress for the leader's entry points (as in qe_follower_step)
@@ -783,7 +784,6 @@ int qe_compact(const qe_progress *p, const qe_compaction *c, uint64_t *stats, vo
   a.applied = c->applied;
   a.snap_term = c->snap_term;
   a.result = c->result;
-  a.stats = stats;
   return dispatch_compact(a, static_cast<hipStream_t>(stream));
 }
 
@@ -801,16 +801,13 @@ int qe_snapshot_step(const qe_progress *p, const qe_follower *f, const qe_conf *
   if (conf_mismatch(p, c)) return QE_EINVAL;
   if (missing_log_model(p)) return QE_EINVAL;
   if (!p->self_slot) return QE_EINVAL;  // restore() looks for the receiver in the ConfState
-  if (!f->term || !f->state || !f->lead || !out->result) return QE_EINVAL;
+  if (missing_follower(f) || !out->result) return QE_EINVAL;
   if (!m->type || !m->from || !m->term || !m->snap_index || !m->snap_term || !m->cs_inc ||
       !m->cs_out || !m->cs_learner || !m->cs_learners_next || !m->cs_auto_leave)
     return QE_EINVAL;
   if (p->num_groups == 0) return QE_OK;
   SNArgs a{};
-  a.G = p->num_groups;
-  a.goff = p->group_offset;
-  a.stride = p->stride;
-  a.R = p->log_runs;
+  step_head(p, stats, a);
   a.S = p->num_slots;
   a.committed = p->committed;
   a.last_index = const_cast<uint64_t *>(p->last_index);
@@ -847,7 +844,6 @@ int qe_snapshot_step(const qe_progress *p, const qe_follower *f, const qe_conf *
   a.result = out->result;
   a.resp_index = out->resp_index;
   a.events = out->events;
-  a.stats = stats;
   return dispatch_snap(a, static_cast<hipStream_t>(stream));
 }
 

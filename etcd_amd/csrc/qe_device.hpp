@@ -332,10 +332,32 @@ __device__ __forceinline__ void block_stats_add(uint64_t (&c)[NC], const int (&i
 #pragma unroll
     for (int i = 0; i < NC; i++)
       if (i == static_cast<int>(threadIdx.x)) which = idx[i];
-    const int shard = blockIdx.x & 63;  // QE_STATS_SHARDS
-    atomicAdd(reinterpret_cast<unsigned long long *>(stats + shard * 16 + which),
+    // the block's shard (QE_STATS_SHARDS) of 16 counters
+    atomicAdd(reinterpret_cast<unsigned long long *>(stats + (blockIdx.x & 63) * 16 + which),
               static_cast<unsigned long long>(s));
   }
+}
+
+// The same without LDS, for the kernels whose waves walk a capped grid
+// (qe_launch.hpp tile_grid): wave sums, then lane i issues the atomic of
+// counter i, one atomic per counter per wave.
+template <int NC>
+__device__ __forceinline__ void wave_stats_add(const uint64_t (&c)[NC], const int (&idx)[NC],
+                                               uint64_t *stats) {
+  const uint32_t lane = threadIdx.x & 63;
+  uint64_t v = 0;
+  int which = 0;
+#pragma unroll
+  for (int i = 0; i < NC; i++) {
+    const uint64_t s = wave_sum_u64(c[i]);
+    if (lane == static_cast<uint32_t>(i)) {
+      v = s;
+      which = idx[i];
+    }
+  }
+  if (lane < NC)
+    atomicAdd(reinterpret_cast<unsigned long long *>(stats + (blockIdx.x & 63) * 16 + which),
+              static_cast<unsigned long long>(v));
 }
 
 }  // namespace qe

@@ -5,10 +5,7 @@
 // findConflictByTerm / commitTo (raft/log.go:88-168, :233-241) on the term-run
 // log model, one message per group (include/etcd_quorum.h states the rules).
 //
-// The house idiom of k_tick / k_heartbeat: one lane per group, one wave per
-// 64-group tile, per-tile buffer descriptors, a conditional access = an
-// unconditional one whose offset is pushed out of range, every store after
-// every load of the tile.  Per tile:
+// The house idiom (qe_step.hpp).  Per tile:
 //   1. type (1 B): which lanes have a message (a tile with none ends here);
 //   2. for those lanes: from, m.Term, r.Term, state, m.Commit, committed,
 //      last_index; for the MsgApp lanes m.Index, m.LogTerm and the E entry
@@ -20,7 +17,6 @@
 //   4. the stores, each under the ballot of the lanes that changed the row: a
 //      run row is stored only when some lane wrote it, so the common case (a
 //      same-term append at the tail) stores no run row and no run_count.
-// Every row is touched once per launch: all accesses go non-temporal.
 //
 // RM is the run-capacity bucket (log_runs <= 4 / 8 / 16), ENT whether the
 // launch carries entries (msg_runs > 0): without them findConflict and the
@@ -29,7 +25,7 @@
 // untouched.  The slot count is a run-time bound on `from` only, so the
 // kernel is compiled once, not per QE_S.
 #pragma once
-#include "qe_progress.hpp"
+#include "qe_step.hpp"
 
 namespace qe {
 
@@ -54,24 +50,11 @@ struct FArgs {
   uint64_t *stats;
 };
 
-int hip_status(hipError_t e);
-
 // defined in qe_inst_follow.hip
 int dispatch_follow(const FArgs &a, hipStream_t st);
 
 constexpr uint64_t kFollowSalt = 0x2545F4914F6CDD1Dull;
 constexpr int kMsgRuns = QE_MAX_MSG_RUNS;
-
-// raftLog.term (raft/log.go:265-285) over the runs in registers
-// (oracle/quorum_oracle.c orc_log_term).
-template <int RM>
-__device__ __forceinline__ uint64_t run_term_at(const uint64_t (&rf)[RM], const uint64_t (&rt)[RM],
-                                                uint32_t nr, uint64_t li, uint64_t i) {
-  uint64_t t = 0;
-#pragma unroll
-  for (int r = 0; r < RM; r++) t = (static_cast<uint32_t>(r) < nr && i >= rf[r]) ? rt[r] : t;
-  return (nr == 0 || i < rf[0] || i > li) ? 0 : t;
-}
 
 enum { F_GROUPS, F_ACCEPT, F_REJECT, F_APPENDED, F_ADV, F_REFUSED, F_CSUM, F_N };
 
@@ -83,13 +66,9 @@ __global__ __launch_bounds__(kBlock) void k_follow(FArgs a) {
   tile_walk(a.G, lane, wave, nwaves, ntiles);
   const bool resp_low = a.flags != 0;
   for (uint64_t t = wave; t < ntiles; t += nwaves) {
-    const uint64_t g0 = t * 64;
-    const uint32_t n = tile_n(a.G, t);
-    const uint32_t o8 = lane * 8;
-    const bool live = lane < n;
-    const uint64_t gid = a.goff + g0 + lane;
+    const auto [g0, n, o8, live, gid] = tile_at(a.G, a.goff, t, lane);
     // ---- 1. who has a message ----
-    const uint32_t ty = bld8<kNT>(mk_rsrc(a.type + g0, n), lane);
+    const uint32_t ty = msg_type(a.type, g0, n, lane);
     const bool has = live && ty != QE_LMSG_NONE;
     uint32_t res = QE_FR_NONE, ev = 0;
     if (__builtin_amdgcn_ballot_w64(has)) {
@@ -265,17 +244,7 @@ __global__ __launch_bounds__(kBlock) void k_follow(FArgs a) {
       const bool w_rej = rej && ok;
       // ---- 4. the stores ----
       const bool w_term = okbf && higher;
-      if (__builtin_amdgcn_ballot_w64(w_term)) {
-        bst64<kNT>(mterm, mk_rsrc(a.term + g0, n * 8), w_term ? o8 : kOOB);
-        bst8<kNT>(0xFFu, opt_rsrc(a.vote, g0, n), w_term ? lane : kOOB);
-      }
-      if (__builtin_amdgcn_ballot_w64(okbf)) {
-        const bool w_st = okbf && st != QE_STATE_FOLLOWER;
-        bst8<kNT>(QE_STATE_FOLLOWER, mk_rsrc(a.state + g0, n), w_st ? lane : kOOB);
-        bst8<kNT>(0xFFu, opt_rsrc(a.transferee, g0, n), okbf ? lane : kOOB);
-      }
-      if (__builtin_amdgcn_ballot_w64(ok))
-        bst8<kNT>(from, mk_rsrc(a.lead + g0, n), ok ? lane : kOOB);
+      become_follower_stores(a, g0, n, lane, w_term, okbf, ok, mterm, st, from);
       if (__builtin_amdgcn_ballot_w64(w_commit))
         bst64<kNT>(new_c, mk_rsrc(a.committed + g0, n * 8), w_commit ? o8 : kOOB);
       if constexpr (ENT) {
@@ -321,28 +290,14 @@ __global__ __launch_bounds__(kBlock) void k_follow(FArgs a) {
         cnt[F_CSUM] += has ? h : 0u;
       }
     }
-    bst8<kNT>(res, mk_rsrc(a.result + g0, n), lane);
-    bst8<kNT>(ev, opt_rsrc(a.events, g0, n), lane);
+    st_result_events(a.result, a.events, g0, n, lane, res, ev);
   }
   if (a.stats) {
-    // wave sums, one atomic per counter per wave (no LDS), as k_tick
     const int idx[F_N] = {QE_STAT_GROUPS,          QE_STAT_GRANTED,
                           QE_STAT_REJECTED,        QE_STAT_FOLLOW_APPENDED,
                           QE_STAT_COMMIT_ADVANCED, QE_STAT_INVARIANT_VIOLATIONS,
                           QE_STAT_CHECKSUM};
-    uint64_t v = 0;
-    int which = 0;
-#pragma unroll
-    for (int i = 0; i < F_N; i++) {
-      const uint64_t s = wave_sum_u64(cnt[i]);
-      if (lane == static_cast<uint32_t>(i)) {
-        v = s;
-        which = idx[i];
-      }
-    }
-    if (lane < F_N)
-      atomicAdd(reinterpret_cast<unsigned long long *>(a.stats + (blockIdx.x & 63) * 16 + which),
-                static_cast<unsigned long long>(v));
+    wave_stats_add<F_N>(cnt, idx, a.stats);
   }
 }
 

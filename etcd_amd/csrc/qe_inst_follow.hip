@@ -17,14 +17,9 @@ int launch_follow(const FArgs &a, dim3 grid, hipStream_t st) {
 }
 }  // namespace
 
-// One tile per wave (as qe_tick).  With statistics the grid is capped and the
-// waves walk: every wave ends with one atomic per counter.
+// One tile per wave (qe_launch.hpp tile_grid).
 int dispatch_follow(const FArgs &a, hipStream_t st) {
-  const uint64_t tiles = (a.G + 63) / 64;
-  uint64_t blocks = (tiles + (kBlock / 64) - 1) / (kBlock / 64);
-  const uint64_t cap = a.stats ? static_cast<uint64_t>(num_cus()) * 8 : 0x7FFFFFFFull;
-  if (blocks > cap) blocks = cap;
-  const dim3 grid(static_cast<unsigned>(blocks ? blocks : 1));
+  const dim3 grid(tile_grid(a.G, num_cus(), a.stats != nullptr));
   if (a.R <= 4) return launch_follow<4>(a, grid, st);
   if (a.R <= 8) return launch_follow<8>(a, grid, st);
   return launch_follow<16>(a, grid, st);

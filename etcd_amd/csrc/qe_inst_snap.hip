@@ -6,20 +6,9 @@
 
 namespace qe {
 
-namespace {
-// One tile per wave (as qe_follower_step).  With statistics the grid is capped
-// and the waves walk: every wave ends with one atomic per counter.
-dim3 tile_grid(uint64_t G, bool stats) {
-  const uint64_t tiles = (G + 63) / 64;
-  uint64_t blocks = (tiles + (kBlock / 64) - 1) / (kBlock / 64);
-  const uint64_t cap = stats ? static_cast<uint64_t>(num_cus()) * 8 : 0x7FFFFFFFull;
-  if (blocks > cap) blocks = cap;
-  return dim3(static_cast<unsigned>(blocks ? blocks : 1));
-}
-}  // namespace
-
+// One tile per wave (qe_launch.hpp tile_grid).
 int dispatch_compact(const CPArgs &a, hipStream_t st) {
-  const dim3 grid = tile_grid(a.G, a.stats != nullptr);
+  const dim3 grid(tile_grid(a.G, num_cus(), a.stats != nullptr));
   if (a.R <= 4)
     hipLaunchKernelGGL(k_compact<4>, grid, dim3(kBlock), 0, st, a);
   else if (a.R <= 8)
@@ -30,7 +19,7 @@ int dispatch_compact(const CPArgs &a, hipStream_t st) {
 }
 
 int dispatch_snap(const SNArgs &a, hipStream_t st) {
-  const dim3 grid = tile_grid(a.G, a.stats != nullptr);
+  const dim3 grid(tile_grid(a.G, num_cus(), a.stats != nullptr));
   if (a.S <= 8)
     hipLaunchKernelGGL(k_snap<uint8_t>, grid, dim3(kBlock), 0, st, a);
   else

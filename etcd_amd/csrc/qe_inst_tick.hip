@@ -14,16 +14,11 @@ constexpr int S = QE_S;
 using MT = std::conditional<(S <= 8), uint8_t, uint16_t>::type;
 }  // namespace
 
-// One tile per wave (as qe_heartbeat).  With statistics the grid is capped
-// and the waves walk: every wave ends with one atomic per counter.
+// One tile per wave (qe_launch.hpp tile_grid).
 template <int N>
 int dispatch_tick(const TArgs &a, bool masked, bool joint, hipStream_t st) {
   static_assert(N == S, "one slot count per object");
-  const uint64_t tiles = (a.G + 63) / 64;
-  uint64_t blocks = (tiles + (kBlock / 64) - 1) / (kBlock / 64);
-  const uint64_t cap = a.stats ? static_cast<uint64_t>(num_cus()) * 8 : 0x7FFFFFFFull;
-  if (blocks > cap) blocks = cap;
-  const dim3 grid(static_cast<unsigned>(blocks ? blocks : 1));
+  const dim3 grid(tile_grid(a.G, num_cus(), a.stats != nullptr));
   return with_quorum_form(masked, joint, [&](auto m, auto j) {
     hipLaunchKernelGGL((k_tick<S, MT, m(), j()>), grid, dim3(kBlock), 0, st, a);
     return hip_status(hipGetLastError());

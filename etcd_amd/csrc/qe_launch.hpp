@@ -1,8 +1,8 @@
 // qe_launch.hpp — the launch rules every kernel family shares: the
-// tiles-per-wave chunk plan and the helpers that turn run-time choices (slot
-// count, quorum form, non-temporal bits) into compile-time constants.  Plain
-// C++17 with no HIP in it, so a host-only program can include it
-// (tests/cpp/chunk_plan_test.cpp).
+// tiles-per-wave chunk plan, the one-tile-per-wave grid with its statistics
+// cap, and the helpers that turn run-time choices (slot count, quorum form,
+// non-temporal bits) into compile-time constants.  Plain C++17 with no HIP in
+// it, so a host-only program can include it (tests/cpp/chunk_plan_test.cpp).
 #pragma once
 #include <stdint.h>
 
@@ -43,6 +43,19 @@ inline ChunkPlan chunk_plan(uint64_t tiles, int cus, int tpw_override, uint32_t 
   const uint64_t blocks = (tiles + per_block - 1) / per_block;
   if (blocks > 0x7FFFFFFFull) return {QE_ERANGE, 0, 0};
   return {QE_OK, static_cast<uint32_t>(chunk), static_cast<uint32_t>(blocks)};
+}
+
+// The grid of a kernel that gives each wave one 64-group tile (qe_tick and
+// the step kernels): a block per kBlock / 64 tiles, at least one.  With
+// statistics it is capped at 8 blocks per CU and the waves walk, since every
+// wave ends with one atomic per counter; without, at the 2^31 - 1 blocks of a
+// launch.
+inline uint32_t tile_grid(uint64_t groups, int cus, bool stats) {
+  const uint64_t tiles = (groups + 63) / 64;
+  uint64_t blocks = (tiles + (kBlock / 64) - 1) / (kBlock / 64);
+  const uint64_t cap = stats ? static_cast<uint64_t>(cus) * 8 : 0x7FFFFFFFull;
+  if (blocks > cap) blocks = cap;
+  return static_cast<uint32_t>(blocks ? blocks : 1);
 }
 
 // The three quorum forms the kernels are built for: f(MASKED, JOINT) with

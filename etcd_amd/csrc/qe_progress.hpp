@@ -36,108 +36,11 @@
 // condition is false (no traffic, no branch, loads return 0).  Accesses that
 // are rare for a whole wave sit behind real (wave-uniform) branches.
 #pragma once
-#include "qe_stream.hpp"
+#include "qe_tile.hpp"
 
 namespace qe {
 
 constexpr int kRingChunk = 8;  // F <= kRingChunk: the ring lives in registers (row form)
-
-// Cache policy of the Progress kernels' accesses (the helpers' AUX: 0 =
-// default, 2 = non-temporal).  The Progress step re-touches the lines it
-// loads (non-temporal loads: +15 %) and so does CheckQuorum (+17 %); the send
-// kernel's appends and Progress rows go non-temporal, kNT: -9 %
-// (profiles/r04/pstep_ab.txt, send_cq_nt_ab.txt).
-// QE_LD_AUX / QE_ST_AUX: A/B knobs for the default.
-#ifndef QE_LD_AUX
-#define QE_LD_AUX 0
-#endif
-#ifndef QE_ST_AUX
-#define QE_ST_AUX 0
-#endif
-#ifndef QE_SEND_AUX  // A/B knob: the send kernel's policy
-#define QE_SEND_AUX 2
-#endif
-constexpr int kNT = QE_SEND_AUX;
-template <int AUX = QE_LD_AUX>
-__device__ __forceinline__ uint64_t bld64(rsrc_t r, uint32_t off) {
-  return __builtin_bit_cast(uint64_t, __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, AUX));
-}
-template <int AUX = QE_LD_AUX>
-__device__ __forceinline__ uint32_t bld8(rsrc_t r, uint32_t off) {
-  return __builtin_amdgcn_raw_buffer_load_b8(r, off, 0, AUX);
-}
-template <int AUX = QE_ST_AUX>
-__device__ __forceinline__ void bst64(uint64_t v, rsrc_t r, uint32_t off) {
-  typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-  __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), r, off, 0, AUX);
-}
-template <int AUX = QE_ST_AUX>
-__device__ __forceinline__ void bst8(uint32_t v, rsrc_t r, uint32_t off) {
-  __builtin_amdgcn_raw_buffer_store_b8(static_cast<uint8_t>(v), r, off, 0, AUX);
-}
-template <int AUX = QE_LD_AUX>
-__device__ __forceinline__ uint32_t bld32(rsrc_t r, uint32_t off) {
-  return __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, AUX);
-}
-template <int AUX = QE_ST_AUX>
-__device__ __forceinline__ void bst32(uint32_t v, rsrc_t r, uint32_t off) {
-  __builtin_amdgcn_raw_buffer_store_b32(v, r, off, 0, AUX);
-}
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ u32x4 bld128(rsrc_t r, uint32_t off) {
-  return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, QE_LD_AUX));
-}
-__device__ __forceinline__ void bst128(u32x4 v, rsrc_t r, uint32_t off) {
-  __builtin_amdgcn_raw_buffer_store_b128(v, r, off, 0, QE_ST_AUX);
-}
-template <typename MT>
-__device__ __forceinline__ void bst_mask(uint32_t v, rsrc_t r, uint32_t lane, bool on = true) {
-  const uint32_t off = on ? lane * static_cast<uint32_t>(sizeof(MT)) : kOOB;
-  if constexpr (sizeof(MT) == 1)
-    __builtin_amdgcn_raw_buffer_store_b8(static_cast<uint8_t>(v), r, off, 0, 0);
-  else
-    __builtin_amdgcn_raw_buffer_store_b16(static_cast<uint16_t>(v), r, off, 0, 0);
-}
-
-// ---------------------------------------------------------------------------
-// Idioms the Progress kernels (and k_tick, qe_tick.hpp) share.
-// ---------------------------------------------------------------------------
-// One lane per group, one wave per 64-group tile: the lane, the wave's first
-// tile, the stride of its walk and the tile count.
-__device__ __forceinline__ void tile_walk(uint64_t G, uint32_t &lane, uint64_t &wave,
-                                          uint64_t &nwaves, uint64_t &ntiles) {
-  lane = threadIdx.x & 63;
-  wave = static_cast<uint64_t>(blockIdx.x) * (kBlock / 64) +
-         __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  nwaves = static_cast<uint64_t>(gridDim.x) * (kBlock / 64);
-  ntiles = (G + 63) / 64;
-}
-
-// A tile's row of a configuration mask (tracked, inc_mask, out_mask) clipped
-// to the S slots, for the lanes with `on` (no bytes move for the others).
-template <typename MT, int S>
-__device__ __forceinline__ uint32_t ld_slot_mask(const void *p, uint64_t g0, uint32_t n,
-                                                 uint32_t lane, bool on = true) {
-  const rsrc_t r = mk_rsrc(static_cast<const MT *>(p) + g0, n * sizeof(MT));
-  const uint32_t off = on ? lane * static_cast<uint32_t>(sizeof(MT)) : kOOB;
-  uint32_t v;
-  if constexpr (sizeof(MT) == 1)
-    v = __builtin_amdgcn_raw_buffer_load_b8(r, off, 0, 0);
-  else
-    v = __builtin_amdgcn_raw_buffer_load_b16(r, off, 0, 0);
-  return v & ((1u << S) - 1u);
-}
-
-// The ReadIndex queue: the pending count (a count above the capacity is
-// invalid input) and readOnly.lastPendingRequestCtx, the
-// context of the newest pending request, 0 with none.
-__device__ __forceinline__ uint32_t read_pending(uint32_t count, uint32_t cap) {
-  return count < cap ? count : cap;
-}
-__device__ __forceinline__ uint32_t last_pending_ctx(uint32_t count, uint32_t head, uint32_t cap) {
-  const uint32_t q = read_pending(count, cap);
-  return q ? head + q - 1u : 0u;
-}
 
 // Byte accounting of the instrumented variant (ACCT): the bytes of every
 // access the reference logic needs (field granularity, each once), i.e. the
@@ -169,7 +72,7 @@ constexpr uint64_t kSentSalt = 0xD1B54A32D192ED03ull;
 constexpr uint64_t kReadSalt = 0x8CB92BA72F3D8DD7ull;   // released ReadIndex requests
 constexpr uint64_t kTermSalt = 0x589965CC75374CC3ull;   // first commit in the leader's term
 constexpr uint64_t kTransferSalt = 0x1D8E4E27C47D124Full; // lead_transferee changed
-constexpr uint64_t kQuorumSalt = 0xA0761D6478BD642Full; // CheckQuorum: quorum active
+// (kQuorumSalt, CheckQuorum's, is in qe_tile.hpp: k_tick shares it)
 
 // ---------------------------------------------------------------------------
 // Inflights rings (ABI 4, include/etcd_quorum.h): 32-bit entry words,

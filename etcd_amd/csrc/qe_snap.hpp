@@ -12,11 +12,7 @@
 // confchange.Restore (raft/confchange/restore.go) in mask form
 // (include/etcd_quorum.h states the rules of both).
 //
-// The house idiom of k_follow / k_vote: one lane per group, one wave per
-// 64-group tile, per-tile buffer descriptors, a conditional access = an
-// unconditional one whose offset is pushed out of range, rows read by need
-// under ballots, a row stored only under the ballot of the lanes that changed
-// it.  Every row is touched once per launch: all accesses go non-temporal.
+// The house idiom (qe_step.hpp).
 //
 // k_snap per tile:
 //   1. type (1 B): which lanes have a message (a tile with none ends here,
@@ -39,8 +35,7 @@
 // value, so the object is compiled once, not per QE_S.  Own argument structs:
 // no other kernel's code object changes.  No LDS, no scratch.
 #pragma once
-#include "qe_follow.hpp"
-#include "qe_vote.hpp"
+#include "qe_step.hpp"
 
 namespace qe {
 
@@ -93,25 +88,6 @@ int dispatch_snap(const SNArgs &a, hipStream_t st);
 constexpr uint64_t kCompactSalt = 0xD1B54A32D192ED03ull;
 constexpr uint64_t kSnapSalt = 0x8CB92BA72F3D8DD7ull;
 
-// one atomic per counter per wave (no LDS), as k_follow
-template <int N>
-__device__ __forceinline__ void snap_stats_out(uint64_t *stats, uint32_t lane,
-                                               const uint64_t (&cnt)[N], const int (&idx)[N]) {
-  uint64_t v = 0;
-  int which = 0;
-#pragma unroll
-  for (int i = 0; i < N; i++) {
-    const uint64_t s = wave_sum_u64(cnt[i]);
-    if (lane == static_cast<uint32_t>(i)) {
-      v = s;
-      which = idx[i];
-    }
-  }
-  if (lane < N)
-    atomicAdd(reinterpret_cast<unsigned long long *>(stats + (blockIdx.x & 63) * 16 + which),
-              static_cast<unsigned long long>(v));
-}
-
 enum { K_GROUPS, K_ENTRIES, K_REFUSED, K_CSUM, K_N };
 
 template <int RM>
@@ -121,11 +97,7 @@ __global__ __launch_bounds__(kBlock) void k_compact(CPArgs a) {
   uint64_t wave, nwaves, ntiles;
   tile_walk(a.G, lane, wave, nwaves, ntiles);
   for (uint64_t t = wave; t < ntiles; t += nwaves) {
-    const uint64_t g0 = t * 64;
-    const uint32_t n = tile_n(a.G, t);
-    const uint32_t o8 = lane * 8;
-    const bool live = lane < n;
-    const uint64_t gid = a.goff + g0 + lane;
+    const auto [g0, n, o8, live, gid] = tile_at(a.G, a.goff, t, lane);
     // ---- 1. who has a request ----
     const uint64_t ci = bld64<kNT>(mk_rsrc(a.compact_index + g0, n * 8), o8);
     const uint64_t si = bld64<kNT>(opt_rsrc(a.create_index, g0, n), o8);
@@ -240,7 +212,7 @@ __global__ __launch_bounds__(kBlock) void k_compact(CPArgs a) {
   if (a.stats) {
     const int idx[K_N] = {QE_STAT_GROUPS, QE_STAT_COMPACTED, QE_STAT_INVARIANT_VIOLATIONS,
                           QE_STAT_CHECKSUM};
-    snap_stats_out<K_N>(a.stats, lane, cnt, idx);
+    wave_stats_add<K_N>(cnt, idx, a.stats);
   }
 }
 
@@ -254,13 +226,9 @@ __global__ __launch_bounds__(kBlock) void k_snap(SNArgs a) {
   tile_walk(a.G, lane, wave, nwaves, ntiles);
   const uint32_t full = (1u << a.S) - 1u;
   for (uint64_t t = wave; t < ntiles; t += nwaves) {
-    const uint64_t g0 = t * 64;
-    const uint32_t n = tile_n(a.G, t);
-    const uint32_t o8 = lane * 8;
-    const bool live = lane < n;
-    const uint64_t gid = a.goff + g0 + lane;
+    const auto [g0, n, o8, live, gid] = tile_at(a.G, a.goff, t, lane);
     // ---- 1. who has a message ----
-    const uint32_t ty = bld8<kNT>(mk_rsrc(a.type + g0, n), lane);
+    const uint32_t ty = msg_type(a.type, g0, n, lane);
     const bool has = live && ty != QE_SMSG_NONE;
     uint32_t res = QE_SR_NONE, ev = 0;
     if (__builtin_amdgcn_ballot_w64(has)) {
@@ -291,10 +259,10 @@ __global__ __launch_bounds__(kBlock) void k_snap(SNArgs a) {
         const uint32_t n1 = need ? lane : kOOB;
         self = bld8<kNT>(mk_rsrc(a.self_slot + g0, n), n1);
         self = need ? self : 0xFFu;
-        mi = vld_mask<MT>(a.m_inc, g0, n, lane, need);
-        mo = vld_mask<MT>(a.m_out, g0, n, lane, need);
-        ml = vld_mask<MT>(a.m_lrn, g0, n, lane, need);
-        mn = vld_mask<MT>(a.m_lnx, g0, n, lane, need);
+        mi = ld_mask<MT, kNT>(mask_rsrc<MT>(a.m_inc, g0, n), lane, need);
+        mo = ld_mask<MT, kNT>(mask_rsrc<MT>(a.m_out, g0, n), lane, need);
+        ml = ld_mask<MT, kNT>(mask_rsrc<MT>(a.m_lrn, g0, n), lane, need);
+        mn = ld_mask<MT, kNT>(mask_rsrc<MT>(a.m_lnx, g0, n), lane, need);
         mauto = bld8<kNT>(mk_rsrc(a.m_auto + g0, n), n1) != 0 ? 1u : 0u;
         sterm = bld64<kNT>(mk_rsrc(a.sterm + g0, n * 8), need ? o8 : kOOB);
         nr = bld8<kNT>(mk_rsrc(a.run_count + g0, n), n1);
@@ -350,17 +318,7 @@ __global__ __launch_bounds__(kBlock) void k_snap(SNArgs a) {
       const uint64_t ridx = (ff || rest) ? sindex : committed;
       // ---- 5. the stores ----
       const bool w_term = okbf && higher;
-      if (__builtin_amdgcn_ballot_w64(w_term)) {
-        bst64<kNT>(mterm, mk_rsrc(a.term + g0, n * 8), w_term ? o8 : kOOB);
-        bst8<kNT>(0xFFu, opt_rsrc(a.vote, g0, n), w_term ? lane : kOOB);
-      }
-      if (__builtin_amdgcn_ballot_w64(okbf)) {
-        const bool w_st = okbf && st != QE_STATE_FOLLOWER;
-        bst8<kNT>(QE_STATE_FOLLOWER, mk_rsrc(a.state + g0, n), w_st ? lane : kOOB);
-        bst8<kNT>(0xFFu, opt_rsrc(a.transferee, g0, n), okbf ? lane : kOOB);
-      }
-      if (__builtin_amdgcn_ballot_w64(ok))
-        bst8<kNT>(from, mk_rsrc(a.lead + g0, n), ok ? lane : kOOB);
+      become_follower_stores(a, g0, n, lane, w_term, okbf, ok, mterm, st, from);
       if (__builtin_amdgcn_ballot_w64(w_commit))
         bst64<kNT>(sindex, mk_rsrc(a.committed + g0, n * 8), w_commit ? o8 : kOOB);
       if (__builtin_amdgcn_ballot_w64(rest)) {
@@ -374,12 +332,12 @@ __global__ __launch_bounds__(kBlock) void k_snap(SNArgs a) {
         bst64<kNT>(sindex, opt_rsrc(a.snap_index, g0, n), r8);
         // the tracker.Config confchange.Restore builds from the ConfState
         const uint32_t trk = mi | mo | ml;
-        vst_mask<MT>(mi, a.c_inc, g0, n, lane, rest);
-        vst_mask<MT>(mo, a.c_out, g0, n, lane, rest);
-        vst_mask<MT>(ml, a.c_lrn, g0, n, lane, rest);
-        vst_mask<MT>(mn, a.c_lnx, g0, n, lane, rest);
-        vst_mask<MT>(ml, a.c_isl, g0, n, lane, rest);
-        vst_mask<MT>(trk, a.c_trk, g0, n, lane, rest);
+        bst_mask<MT, kNT>(mi, mask_rsrc<MT>(a.c_inc, g0, n), lane, rest);
+        bst_mask<MT, kNT>(mo, mask_rsrc<MT>(a.c_out, g0, n), lane, rest);
+        bst_mask<MT, kNT>(ml, mask_rsrc<MT>(a.c_lrn, g0, n), lane, rest);
+        bst_mask<MT, kNT>(mn, mask_rsrc<MT>(a.c_lnx, g0, n), lane, rest);
+        bst_mask<MT, kNT>(ml, mask_rsrc<MT>(a.c_isl, g0, n), lane, rest);
+        bst_mask<MT, kNT>(trk, mask_rsrc<MT>(a.c_trk, g0, n), lane, rest);
         bst8<kNT>(mauto, opt_rsrc(a.c_auto, g0, n), r1);
         if (a.slot_ids && a.m_ids) {
           for (uint32_t s = 0; s < a.S; s++) {
@@ -405,14 +363,13 @@ __global__ __launch_bounds__(kBlock) void k_snap(SNArgs a) {
         cnt[N_CSUM] += has ? h : 0u;
       }
     }
-    bst8<kNT>(res, mk_rsrc(a.result + g0, n), lane);
-    bst8<kNT>(ev, opt_rsrc(a.events, g0, n), lane);
+    st_result_events(a.result, a.events, g0, n, lane, res, ev);
   }
   if (a.stats) {
     const int idx[N_N] = {QE_STAT_GROUPS,          QE_STAT_GRANTED,
                           QE_STAT_REJECTED,        QE_STAT_COMMIT_ADVANCED,
                           QE_STAT_INVARIANT_VIOLATIONS, QE_STAT_CHECKSUM};
-    snap_stats_out<N_N>(a.stats, lane, cnt, idx);
+    wave_stats_add<N_N>(cnt, idx, a.stats);
   }
 }
 

@@ -5,10 +5,8 @@
 // pass: with HeartbeatTick 1 every leader beats on every tick, so the tick is
 // the heartbeat stream plus seven timer bytes per group.
 //
-// The house idiom of k_heartbeat / k_check_quorum (qe_progress.hpp): one lane
-// per group, one wave per 64-group tile, per-tile buffer descriptors, a
-// conditional access = an unconditional one whose offset is pushed out of
-// range.  Per tile:
+// The house idiom (qe_step.hpp), as k_heartbeat / k_check_quorum
+// (qe_progress.hpp).  Per tile:
 //   1. the header: state (1 B), timer (4 B), randomizedElectionTimeout (2 B),
 //      events (1 B) -> the timers and which of CheckQuorum / beat / campaign
 //      fire (wave-wide ballots);
@@ -26,7 +24,7 @@
 // added with one atomic per counter per wave (the grid is capped when
 // statistics are asked for).
 #pragma once
-#include "qe_progress.hpp"
+#include "qe_step.hpp"
 
 namespace qe {
 
@@ -59,23 +57,12 @@ struct TArgs {
   uint64_t *stats;
 };
 
-int hip_status(hipError_t e);
-
 // defined in qe_inst_tick.hip and instantiated there for the object's QE_S
 template <int S>
 int dispatch_tick(const TArgs &a, bool masked, bool joint, hipStream_t st);
 
 constexpr uint32_t kDrawStream = 0x7131;  // hash4 stream of the timeout draw
 constexpr uint32_t kTimerMax = 0xFFFFu;   // the counters saturate here
-
-template <int AUX = QE_LD_AUX>
-__device__ __forceinline__ uint32_t bld16(rsrc_t r, uint32_t off) {
-  return __builtin_amdgcn_raw_buffer_load_b16(r, off, 0, AUX);
-}
-template <int AUX = QE_ST_AUX>
-__device__ __forceinline__ void bst16(uint32_t v, rsrc_t r, uint32_t off) {
-  __builtin_amdgcn_raw_buffer_store_b16(static_cast<uint16_t>(v), r, off, 0, AUX);
-}
 
 // resetRandomizedElectionTimeout (raft/raft.go:1718-1720): electionTimeout +
 // a uniform value of [0, electionTimeout), counter-based (the global group
@@ -97,11 +84,8 @@ __global__ __launch_bounds__(kBlock) void k_tick(TArgs a) {
   const bool cq_on = (a.flags & QE_TICK_CHECK_QUORUM) != 0;
   const bool want_ctx = a.hb_ctx && a.read_acks;
   for (uint64_t t = wave; t < ntiles; t += nwaves) {
-    const uint64_t g0 = t * 64;
-    const uint32_t n = tile_n(a.G, t);
-    const uint32_t o8 = lane * 8, o4 = lane * 4;
-    const bool live = lane < n;
-    const uint64_t gid = a.goff + g0 + lane;
+    const auto [g0, n, o8, live, gid] = tile_at(a.G, a.goff, t, lane);
+    const uint32_t o4 = lane * 4;
     // ---- 1. the header ----
     const uint32_t st0 = bld8<kNT>(mk_rsrc(a.state + g0, n), lane);
     const uint32_t tm0 = bld32<kNT>(mk_rsrc(a.timer + g0, n * 4), o4);
@@ -252,21 +236,8 @@ __global__ __launch_bounds__(kBlock) void k_tick(TArgs a) {
     }
   }
   if (a.stats) {
-    // wave sums, one atomic per counter per wave (no LDS)
     const int idx[T_N] = {QE_STAT_GROUPS, QE_STAT_ELECTIONS, QE_STAT_STEPDOWNS, QE_STAT_CHECKSUM};
-    uint64_t v = 0;
-    int which = 0;
-#pragma unroll
-    for (int i = 0; i < T_N; i++) {
-      const uint64_t s = wave_sum_u64(cnt[i]);
-      if (lane == static_cast<uint32_t>(i)) {
-        v = s;
-        which = idx[i];
-      }
-    }
-    if (lane < T_N)
-      atomicAdd(reinterpret_cast<unsigned long long *>(a.stats + (blockIdx.x & 63) * 16 + which),
-                static_cast<unsigned long long>(v));
+    wave_stats_add<T_N>(cnt, idx, a.stats);
   }
 }
 

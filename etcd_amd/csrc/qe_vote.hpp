@@ -6,10 +6,7 @@
 // becomeFollower / becomePreCandidate / becomeCandidate / becomeLeader, one
 // message per group (include/etcd_quorum.h states the rules).
 //
-// The house idiom of k_follow / k_tick: one lane per group, one wave per
-// 64-group tile, per-tile buffer descriptors, a conditional access = an
-// unconditional one whose offset is pushed out of range, every store after
-// every load of the tile.  Rows are read by need.  Per tile:
+// The house idiom (qe_step.hpp).  Per tile:
 //   1. type (1 B): which lanes have a message (a tile with none ends here);
 //   2. for those lanes: from, m.Term, the flags, r.Term, state, lead, vote;
 //      m.Index and m.LogTerm for requests; in a candidate launch self_slot for
@@ -22,7 +19,6 @@
 //      tile's lanes that need the log (the one round trip that depends on a
 //      loaded value; log_runs == 1 skips run_count);
 //   5. the stores, each under the ballot of the lanes that changed the row.
-// Every row is touched once per launch: all accesses go non-temporal.
 //
 // The lanes of step 3 are known before the lease is (the timer is in flight
 // with the other rows), so they are a superset: a request that turns out to be
@@ -36,7 +32,7 @@
 // the object is compiled once, not per QE_S.  Its own argument struct: no
 // other kernel's code object changes.  No LDS, no scratch.
 #pragma once
-#include "qe_progress.hpp"
+#include "qe_step.hpp"
 
 namespace qe {
 
@@ -68,35 +64,10 @@ struct VArgs {
   uint64_t *stats;
 };
 
-int hip_status(hipError_t e);
-
 // defined in qe_inst_vote.hip
 int dispatch_vote(const VArgs &a, hipStream_t st);
 
 constexpr uint64_t kVoteSalt = 0x9FB21C651E98DF25ull;
-
-// a tile's row of a mask-typed array for the lanes with `on`; a NULL array
-// reads as 0 and drops its stores
-template <typename MT>
-__device__ __forceinline__ uint32_t vld_mask(const void *p, uint64_t g0, uint32_t n, uint32_t lane,
-                                             bool on) {
-  const rsrc_t r = opt_rsrc(static_cast<const MT *>(p), g0, n);
-  const uint32_t off = on ? lane * static_cast<uint32_t>(sizeof(MT)) : kOOB;
-  if constexpr (sizeof(MT) == 1)
-    return __builtin_amdgcn_raw_buffer_load_b8(r, off, 0, kNT);
-  else
-    return __builtin_amdgcn_raw_buffer_load_b16(r, off, 0, kNT);
-}
-template <typename MT>
-__device__ __forceinline__ void vst_mask(uint32_t v, void *p, uint64_t g0, uint32_t n,
-                                         uint32_t lane, bool on) {
-  const rsrc_t r = opt_rsrc(static_cast<const MT *>(p), g0, n);
-  const uint32_t off = on ? lane * static_cast<uint32_t>(sizeof(MT)) : kOOB;
-  if constexpr (sizeof(MT) == 1)
-    __builtin_amdgcn_raw_buffer_store_b8(static_cast<uint8_t>(v), r, off, 0, kNT);
-  else
-    __builtin_amdgcn_raw_buffer_store_b16(static_cast<uint16_t>(v), r, off, 0, kNT);
-}
 
 enum { V_GROUPS, V_GRANT, V_REJECT, V_PENDING, V_ELECT, V_LEADERS, V_DOWN, V_REFUSED, V_CSUM, V_N };
 
@@ -110,13 +81,9 @@ __global__ __launch_bounds__(kBlock) void k_vote(VArgs a) {
   const bool cq_on = (a.flags & QE_VOTE_CHECK_QUORUM) != 0;
   const bool pv_on = (a.flags & QE_VOTE_PREVOTE) != 0;
   for (uint64_t t = wave; t < ntiles; t += nwaves) {
-    const uint64_t g0 = t * 64;
-    const uint32_t n = tile_n(a.G, t);
-    const uint32_t o8 = lane * 8;
-    const bool live = lane < n;
-    const uint64_t gid = a.goff + g0 + lane;
+    const auto [g0, n, o8, live, gid] = tile_at(a.G, a.goff, t, lane);
     // ---- 1. who has a message ----
-    const uint32_t ty = bld8<kNT>(mk_rsrc(a.type + g0, n), lane);
+    const uint32_t ty = msg_type(a.type, g0, n, lane);
     const bool has = live && ty != QE_VMSG_NONE;
     uint32_t res = QE_VR_NONE, ev = 0, el = 0;
     if (__builtin_amdgcn_ballot_w64(has)) {
@@ -190,15 +157,16 @@ __global__ __launch_bounds__(kBlock) void k_vote(VArgs a) {
         const bool needm = mine || hupgo;
         const bool ldv = needm || (a.stats && has);  // (the checksum covers the Votes)
         if (__builtin_amdgcn_ballot_w64(ldv)) {
-          vd = vld_mask<MT>(a.voted, g0, n, lane, ldv);
-          gr = vld_mask<MT>(a.granted, g0, n, lane, ldv);
+          vd = ld_mask<MT, kNT>(mask_rsrc<MT>(a.voted, g0, n), lane, ldv);
+          gr = ld_mask<MT, kNT>(mask_rsrc<MT>(a.granted, g0, n), lane, ldv);
         }
         if (__builtin_amdgcn_ballot_w64(needm)) {
-          if (a.inc) mi = vld_mask<MT>(a.inc, g0, n, lane, needm) & full;
-          if (a.out) mo = vld_mask<MT>(a.out, g0, n, lane, needm) & full;
+          if (a.inc) mi = ld_mask<MT, kNT>(mask_rsrc<MT>(a.inc, g0, n), lane, needm) & full;
+          if (a.out) mo = ld_mask<MT, kNT>(mask_rsrc<MT>(a.out, g0, n), lane, needm) & full;
         }
         if (__builtin_amdgcn_ballot_w64(hupgo)) {
-          if (a.tracked) trk = vld_mask<MT>(a.tracked, g0, n, lane, hupgo) & full;
+          if (a.tracked)
+            trk = ld_mask<MT, kNT>(mask_rsrc<MT>(a.tracked, g0, n), lane, hupgo) & full;
           nc = bld8<kNT>(opt_rsrc(a.no_campaign, g0, n), hupgo ? lane : kOOB);
         }
       }
@@ -305,15 +273,15 @@ __global__ __launch_bounds__(kBlock) void k_vote(VArgs a) {
       if constexpr (CAND) {
         const bool w_m = bf || rec || lost || prec || cand || won;
         if (__builtin_amdgcn_ballot_w64(w_m)) {
-          vst_mask<MT>(vd2, a.voted, g0, n, lane, w_m);
-          vst_mask<MT>(gr2, a.granted, g0, n, lane, w_m);
+          bst_mask<MT, kNT>(vd2, mask_rsrc<MT>(a.voted, g0, n), lane, w_m);
+          bst_mask<MT, kNT>(gr2, mask_rsrc<MT>(a.granted, g0, n), lane, w_m);
         }
       }
       if (__builtin_amdgcn_ballot_w64(w_resp))
         bst64<kNT>(rterm, opt_rsrc(a.resp_term, g0, n), w_resp ? o8 : kOOB);
       if (__builtin_amdgcn_ballot_w64(w_req)) {
         bst64<kNT>(lt, opt_rsrc(a.req_log_term, g0, n), w_req ? o8 : kOOB);
-        vst_mask<MT>((mi | mo) & ~selfb, a.req_to, g0, n, lane, w_req);
+        bst_mask<MT, kNT>((mi | mo) & ~selfb, mask_rsrc<MT>(a.req_to, g0, n), lane, w_req);
       }
       if (a.stats) {
         uint64_t h = mix64((gid * kPhi) ^ kVoteSalt ^ (static_cast<uint64_t>(res) << 56));
@@ -331,28 +299,14 @@ __global__ __launch_bounds__(kBlock) void k_vote(VArgs a) {
         cnt[V_CSUM] += has ? h : 0u;
       }
     }
-    bst8<kNT>(res, mk_rsrc(a.result + g0, n), lane);
-    bst8<kNT>(ev, opt_rsrc(a.events, g0, n), lane);
+    st_result_events(a.result, a.events, g0, n, lane, res, ev);
     bst8<kNT>(el, opt_rsrc(a.elected, g0, n), lane);
   }
   if (a.stats) {
-    // wave sums, one atomic per counter per wave (no LDS), as k_tick
     const int idx[V_N] = {QE_STAT_GROUPS,    QE_STAT_GRANTED,   QE_STAT_REJECTED,
                           QE_STAT_VOTE_PENDING, QE_STAT_ELECTIONS, QE_STAT_LEADERS,
                           QE_STAT_STEPDOWNS, QE_STAT_INVARIANT_VIOLATIONS, QE_STAT_CHECKSUM};
-    uint64_t v = 0;
-    int which = 0;
-#pragma unroll
-    for (int i = 0; i < V_N; i++) {
-      const uint64_t s = wave_sum_u64(cnt[i]);
-      if (lane == static_cast<uint32_t>(i)) {
-        v = s;
-        which = idx[i];
-      }
-    }
-    if (lane < V_N)
-      atomicAdd(reinterpret_cast<unsigned long long *>(a.stats + (blockIdx.x & 63) * 16 + which),
-                static_cast<unsigned long long>(v));
+    wave_stats_add<V_N>(cnt, idx, a.stats);
   }
 }
 

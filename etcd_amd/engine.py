@@ -784,29 +784,59 @@ def tick(ps, timers, out=None, stats=None, events=None, ticks=1):
     return out
 
 
-def _load_rows(obj, names, arrays):
-    for k, a in arrays.items():
-        if k not in names:
-            raise KeyError(k)
-        dst = getattr(obj, k)
-        a = np.ascontiguousarray(a)
-        if a.dtype == np.uint64:
-            a = a.view(np.int64)
-        elif a.dtype == np.uint32:
-            a = a.view(np.int32)
-        a = a.reshape(-1)
-        dst[: a.size].copy_(torch.from_numpy(a.copy()).to(dst.device))
-    return obj
+_SIGNED = {np.dtype(np.uint64): np.int64, np.dtype(np.uint32): np.int32,
+           np.dtype(np.uint16): np.int16}
 
 
-class Follower:
+class _Rows:
+    """A bundle of device rows described by FIELDS, "name:kind" words with
+    kind u8, u32, u64 (int32 / int64 storage) or mask (u8, or int16 storage of
+    u16); a trailing "?" marks a row the constructor may leave out (None).
+    load_host(**arrays) copies numpy arrays of the unsigned types in (`from`
+    is accepted for `from_`; an array for a row that was left out is dropped);
+    host() returns the rows of HOST (default: all) as numpy arrays of the
+    unsigned types, None for a row left out."""
+
+    FIELDS = ""
+
+    def __init_subclass__(cls):
+        words = [w.rstrip("?").split(":") for w in cls.FIELDS.split()]
+        cls.ARRAYS, cls.KIND = tuple(w[0] for w in words), dict(words)
+        cls.HOST = getattr(cls, "HOST", cls.ARRAYS)
+
+    def load_host(self, **arrays):
+        for k, a in arrays.items():
+            k = "from_" if k == "from" else k
+            if k not in self.ARRAYS:
+                raise KeyError(k)
+            dst = getattr(self, k)
+            if dst is None:
+                continue
+            a = np.ascontiguousarray(a)
+            a = a.view(_SIGNED.get(a.dtype, a.dtype)).reshape(-1)
+            dst[: a.size].copy_(torch.from_numpy(a.copy()).to(dst.device))
+        return self
+
+    def host(self):
+        out = {}
+        for k in self.HOST:
+            t = getattr(self, k)
+            a = None if t is None else t.cpu().numpy()
+            kind = {"u64": np.uint64, "u32": np.uint32, "u8": np.uint8}.get(self.KIND[k])
+            if a is not None:  # (a mask row is u8 up to 8 slots, u16 above)
+                a = a.view(kind or (np.uint8 if a.dtype == np.uint8 else np.uint16))
+            out[k] = a
+        return out
+
+
+class Follower(_Rows):
     """Device-resident receiver state of G groups (qe_follower): `term` int64
     storage of r.Term, `state` u8 QE_STATE_* (pass a Timers' `state` tensor to
     share the row with qe_tick), `lead` and `vote` u8 slots (0xFF = None;
     vote=False leaves the row out).  check_quorum / prevote are the raft.Config
     switches that make a lower-term MsgApp / MsgHeartbeat answered."""
 
-    ARRAYS = ("term", "state", "lead", "vote")
+    FIELDS = "term:u64 state:u8 lead:u8 vote:u8?"
 
     def __init__(self, ps, state=None, vote=True, check_quorum=False, prevote=False):
         dev, u8 = ps.device, torch.uint8
@@ -817,28 +847,19 @@ class Follower:
         self.flags = ((_lib.QE_FOLLOW_CHECK_QUORUM if check_quorum else 0) |
                       (_lib.QE_FOLLOW_PREVOTE if prevote else 0))
 
-    def load_host(self, **arrays):
-        """numpy arrays: term uint64, state / lead / vote uint8."""
-        return _load_rows(self, self.ARRAYS, arrays)
-
     def struct(self):
         return _lib.QeFollower(_ptr(self.term), _ptr(self.state), _ptr(self.lead),
                                _ptr(self.vote), self.flags, 0)
 
-    def host(self):
-        out = {k: (None if getattr(self, k) is None else getattr(self, k).cpu().numpy())
-               for k in self.ARRAYS}
-        out["term"] = out["term"].view(np.uint64)
-        return out
 
-
-class LeaderMsgs:
+class LeaderMsgs(_Rows):
     """One MsgApp / MsgHeartbeat per group for qe_follower_step
     (qe_leader_msgs): type / from_ u8, term / index / log_term / commit int64
     storage of the u64 fields, and the entries of a MsgApp as msg_runs term
     runs: ent_len int32 [E][stride], ent_term int64 [E][stride]."""
 
-    ARRAYS = ("type", "from_", "term", "index", "log_term", "commit", "ent_len", "ent_term")
+    FIELDS = ("type:u8 from_:u8 term:u64 index:u64 log_term:u64 commit:u64 ent_len:u32? "
+              "ent_term:u64?")
 
     def __init__(self, ps, msg_runs=1):
         if not 0 <= int(msg_runs) <= _lib.QE_MAX_MSG_RUNS:
@@ -855,28 +876,19 @@ class LeaderMsgs:
         self.ent_len = torch.zeros(n, dtype=torch.int32, device=dev) if n else None
         self.ent_term = torch.zeros(n, dtype=i64, device=dev) if n else None
 
-    def load_host(self, **arrays):
-        """numpy arrays: type / from_ uint8, term / index / log_term / commit /
-        ent_term uint64, ent_len uint32 (`from` is accepted for `from_`)."""
-        if "from" in arrays:
-            arrays["from_"] = arrays.pop("from")
-        if self.msg_runs == 0:
-            arrays = {k: v for k, v in arrays.items() if k not in ("ent_len", "ent_term")}
-        return _load_rows(self, self.ARRAYS, arrays)
-
     def struct(self):
         return _lib.QeLeaderMsgs(_ptr(self.type), _ptr(self.from_), _ptr(self.term),
                                  _ptr(self.index), _ptr(self.log_term), _ptr(self.commit),
                                  self.msg_runs, 0, _ptr(self.ent_len), _ptr(self.ent_term))
 
 
-class FollowerOut:
+class FollowerOut(_Rows):
     """Outputs of qe_follower_step (qe_follower_out): `result` u8 QE_FR_*,
     resp_index / reject_hint / resp_log_term / append_from int64 [G], and
     `events` u8 QE_TEV_* [G], written for every group, which tick(...,
     events=) takes as it is."""
 
-    ARRAYS = ("result", "resp_index", "reject_hint", "resp_log_term", "append_from", "events")
+    FIELDS = "result:u8 resp_index:u64 reject_hint:u64 resp_log_term:u64 append_from:u64 events:u8"
 
     def __init__(self, ps):
         dev, i64, u8 = ps.device, torch.int64, torch.uint8
@@ -887,20 +899,10 @@ class FollowerOut:
         self.append_from = torch.zeros(ps.G, dtype=i64, device=dev)
         self.events = torch.zeros(ps.G, dtype=u8, device=dev)
 
-    def load_host(self, **arrays):
-        """numpy arrays (e.g. sentinels a test wants to see survive)."""
-        return _load_rows(self, self.ARRAYS, arrays)
-
     def struct(self):
         return _lib.QeFollowerOut(_ptr(self.result), _ptr(self.resp_index),
                                   _ptr(self.reject_hint), _ptr(self.resp_log_term),
                                   _ptr(self.append_from), _ptr(self.events))
-
-    def host(self):
-        out = {k: getattr(self, k).cpu().numpy() for k in self.ARRAYS}
-        for k in ("resp_index", "reject_hint", "resp_log_term", "append_from"):
-            out[k] = out[k].view(np.uint64)
-        return out
 
 
 def follower_step(ps, fol, msgs, out=None, stats=None):
@@ -916,7 +918,7 @@ def follower_step(ps, fol, msgs, out=None, stats=None):
     return out
 
 
-class Voter:
+class Voter(_Rows):
     """The election side of G groups (qe_voter): the Votes map as `voted` /
     `granted` masks [G] (votes=False leaves them out: a voter-only launch,
     which answers requests and refuses responses and campaigns), `no_campaign`
@@ -924,7 +926,8 @@ class Voter:
     lease reads.  Pass `timers` to take timer, no_campaign, election_timeout
     and check_quorum from it."""
 
-    ARRAYS = ("voted", "granted", "no_campaign")
+    FIELDS = "voted:mask? granted:mask? no_campaign:u8?"
+    HOST = ("voted", "granted")
 
     def __init__(self, ps, timers=None, votes=True, check_quorum=None, prevote=False,
                  election_timeout=None, no_campaign=None):
@@ -943,32 +946,17 @@ class Voter:
         self.voted = torch.zeros(ps.G, dtype=md, device=dev) if votes else None
         self.granted = torch.zeros(ps.G, dtype=md, device=dev) if votes else None
 
-    def load_host(self, **arrays):
-        """numpy arrays: voted / granted in the mask type, no_campaign uint8."""
-        for k in ("voted", "granted"):
-            if k in arrays and np.asarray(arrays[k]).dtype == np.uint16:
-                arrays[k] = np.ascontiguousarray(arrays[k]).view(np.int16)
-        return _load_rows(self, self.ARRAYS, arrays)
-
     def struct(self):
         return _lib.QeVoter(_ptr(self.timer), self.election_timeout, self.flags, _ptr(self.voted),
                             _ptr(self.granted), _ptr(self.no_campaign))
 
-    def host(self):
-        out = {}
-        for k in ("voted", "granted"):
-            t = getattr(self, k)
-            out[k] = None if t is None else t.cpu().numpy().view(
-                np.uint8 if t.dtype == torch.uint8 else np.uint16)
-        return out
 
-
-class VoteMsgs:
+class VoteMsgs(_Rows):
     """One election message per group for qe_vote_step (qe_vote_msgs): type
     (QE_VMSG_*) / from_ / flags (QE_VMF_*) u8, term / index / log_term int64
     storage of the u64 fields."""
 
-    ARRAYS = ("type", "from_", "term", "index", "log_term", "flags")
+    FIELDS = "type:u8 from_:u8 term:u64 index:u64 log_term:u64 flags:u8"
 
     def __init__(self, ps):
         dev, i64, u8 = ps.device, torch.int64, torch.uint8
@@ -979,25 +967,18 @@ class VoteMsgs:
         self.log_term = torch.zeros(ps.G, dtype=i64, device=dev)
         self.flags = torch.zeros(ps.G, dtype=u8, device=dev)
 
-    def load_host(self, **arrays):
-        """numpy arrays: type / from_ / flags uint8, term / index / log_term
-        uint64 (`from` is accepted for `from_`)."""
-        if "from" in arrays:
-            arrays["from_"] = arrays.pop("from")
-        return _load_rows(self, self.ARRAYS, arrays)
-
     def struct(self):
         return _lib.QeVoteMsgs(_ptr(self.type), _ptr(self.from_), _ptr(self.term),
                                _ptr(self.index), _ptr(self.log_term), _ptr(self.flags))
 
 
-class VoteOut:
+class VoteOut(_Rows):
     """Outputs of qe_vote_step (qe_vote_out): `result` u8 QE_VR_*, resp_term /
     req_log_term int64 [G], req_to mask [G], and two rows written for every
     group: `elected` u8, which Leader(ps, elected=) takes as it is, and
     `events` u8 QE_TEV_*, which tick(..., events=) takes as it is."""
 
-    ARRAYS = ("result", "resp_term", "req_log_term", "req_to", "elected", "events")
+    FIELDS = "result:u8 resp_term:u64 req_log_term:u64 req_to:mask elected:u8 events:u8"
 
     def __init__(self, ps):
         dev, i64, u8 = ps.device, torch.int64, torch.uint8
@@ -1011,14 +992,6 @@ class VoteOut:
     def struct(self):
         return _lib.QeVoteOut(_ptr(self.result), _ptr(self.resp_term), _ptr(self.req_log_term),
                               _ptr(self.req_to), _ptr(self.elected), _ptr(self.events))
-
-    def host(self):
-        out = {k: getattr(self, k).cpu().numpy() for k in self.ARRAYS}
-        for k in ("resp_term", "req_log_term"):
-            out[k] = out[k].view(np.uint64)
-        if out["req_to"].dtype == np.int16:
-            out["req_to"] = out["req_to"].view(np.uint16)
-        return out
 
 
 def vote_step(ps, fol, voter, msgs, out=None, stats=None):
@@ -1036,20 +1009,14 @@ def vote_step(ps, fol, voter, msgs, out=None, stats=None):
     return out
 
 
-def _masks_i16(arrays):
-    """uint16 mask rows as the int16 storage the tensors use."""
-    return {k: (np.ascontiguousarray(a).view(np.int16) if np.asarray(a).dtype == np.uint16 else a)
-            for k, a in arrays.items()}
-
-
-class Compaction:
+class Compaction(_Rows):
     """One CreateSnapshot and / or Compact request per group for qe_compact
     (qe_compaction): compact_index / create_index / applied int64 storage of
     the u64 rows (0 = no request; create=False / applied=False leave the row
     out: no snapshot is created, the bound is `committed`), and the outputs
     snap_term (term(i) where a snapshot was created) and result (QE_CP_*)."""
 
-    ARRAYS = ("compact_index", "create_index", "applied", "snap_term", "result")
+    FIELDS = "compact_index:u64 create_index:u64? applied:u64? snap_term:u64? result:u8"
 
     def __init__(self, ps, create=True, applied=True):
         dev, i64 = ps.device, torch.int64
@@ -1059,22 +1026,9 @@ class Compaction:
         self.snap_term = torch.zeros(ps.G, dtype=i64, device=dev) if create else None
         self.result = torch.zeros(ps.G, dtype=torch.uint8, device=dev)
 
-    def load_host(self, **arrays):
-        """numpy arrays: the index rows uint64, result uint8."""
-        return _load_rows(self, self.ARRAYS, {k: v for k, v in arrays.items()
-                                              if getattr(self, k) is not None})
-
     def struct(self):
         return _lib.QeCompaction(_ptr(self.compact_index), _ptr(self.create_index),
                                  _ptr(self.applied), _ptr(self.snap_term), _ptr(self.result))
-
-    def host(self):
-        out = {k: (None if getattr(self, k) is None else getattr(self, k).cpu().numpy())
-               for k in self.ARRAYS}
-        for k in self.ARRAYS[:4]:
-            if out[k] is not None:
-                out[k] = out[k].view(np.uint64)
-        return out
 
 
 def compact(ps, cp, stats=None):
@@ -1087,7 +1041,7 @@ def compact(ps, cp, stats=None):
     return cp
 
 
-class SnapMsgs:
+class SnapMsgs(_Rows):
     """One MsgSnap per group for qe_snapshot_step (qe_snap_msgs): type / from_
     u8, term / snap_index / snap_term int64 storage of the u64 fields, the
     ConfState as slot masks in the receiver's numbering (cs_inc, cs_out,
@@ -1095,8 +1049,8 @@ class SnapMsgs:
     [S][stride] (the peer id of each slot)."""
 
     MASKS = ("cs_inc", "cs_out", "cs_learner", "cs_learners_next")
-    ARRAYS = ("type", "from_", "term", "snap_index", "snap_term") + MASKS + ("cs_auto_leave",
-                                                                             "cs_ids")
+    FIELDS = ("type:u8 from_:u8 term:u64 snap_index:u64 snap_term:u64 cs_inc:mask cs_out:mask "
+              "cs_learner:mask cs_learners_next:mask cs_auto_leave:u8 cs_ids:u64?")
 
     def __init__(self, ps, ids=False):
         dev, i64, u8 = ps.device, torch.int64, torch.uint8
@@ -1110,25 +1064,16 @@ class SnapMsgs:
         self.cs_auto_leave = torch.zeros(ps.G, dtype=u8, device=dev)
         self.cs_ids = torch.zeros(ps.S * ps.stride, dtype=i64, device=dev) if ids else None
 
-    def load_host(self, **arrays):
-        """numpy arrays: u8 rows uint8, u64 rows uint64, masks uint8 / uint16
-        (`from` is accepted for `from_`)."""
-        if "from" in arrays:
-            arrays["from_"] = arrays.pop("from")
-        if self.cs_ids is None:
-            arrays.pop("cs_ids", None)
-        return _load_rows(self, self.ARRAYS, _masks_i16(arrays))
-
     def struct(self):
         return _lib.QeSnapMsgs(*[_ptr(getattr(self, k)) for k in self.ARRAYS])
 
 
-class SnapOut:
+class SnapOut(_Rows):
     """Outputs of qe_snapshot_step (qe_snap_out): result u8 QE_SR_*,
     resp_index int64 [G] (the MsgAppResp's index where one goes out) and events
     u8 QE_TEV_* [G], written for every group."""
 
-    ARRAYS = ("result", "resp_index", "events")
+    FIELDS = "result:u8 resp_index:u64 events:u8"
 
     def __init__(self, ps):
         dev = ps.device
@@ -1138,11 +1083,6 @@ class SnapOut:
 
     def struct(self):
         return _lib.QeSnapOut(_ptr(self.result), _ptr(self.resp_index), _ptr(self.events))
-
-    def host(self):
-        out = {k: getattr(self, k).cpu().numpy() for k in self.ARRAYS}
-        out["resp_index"] = out["resp_index"].view(np.uint64)
-        return out
 
 
 def snapshot_step(ps, fol, conf, msgs, out=None, stats=None):

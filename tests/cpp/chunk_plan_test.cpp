@@ -2,7 +2,10 @@
 // the five launch sites it replaced: launch_cv_stream and launch_repl_stream
 // (an override is taken as given), launch_progress_send, launch_check_quorum
 // and qe_confchange (an override is floored at 2 as the automatic chunk is).
-// Host only: no GPU, no library.
+// Host only: no GPU, no library.  And tile_grid, the grid of the kernels that
+// give each wave one tile (the four dispatchers of qe_tick and the step kernels
+// it replaced): a block per 4 tiles, at least 1, with statistics at most 8 per
+// CU.
 //
 // The rule, for `tiles` 64-group tiles, 256 CUs and at most 8 tiles per wave:
 //   automatic chunk = max(2, ceil(tiles / (256 * 32))), then min(8, .);
@@ -25,7 +28,37 @@ static void expect(const char *what, uint64_t tiles, int over, bool floor_over, 
   }
 }
 
+static void expect_grid(const char *what, uint64_t groups, bool stats, uint32_t blocks) {
+  const uint32_t got = qe::tile_grid(groups, 256, stats);
+  if (got != blocks) {
+    failures++;
+    printf("FAIL %s: groups %llu stats %d -> %u blocks, want %u\n", what,
+           static_cast<unsigned long long>(groups), stats ? 1 : 0, got, blocks);
+  }
+}
+
+// 256 CUs: the cap is 2048 blocks = 8192 tiles = 524288 groups
+static void tile_grid_cases() {
+  for (int st = 0; st < 2; st++) {
+    const bool s = st != 0;
+    expect_grid("no group", 0, s, 1);
+    expect_grid("one group", 1, s, 1);
+    expect_grid("one block of tiles", 4 * 64, s, 1);
+    expect_grid("one group more", 4 * 64 + 1, s, 2);
+    expect_grid("one tile more", 5 * 64, s, 2);
+    expect_grid("the cap", 2048ull * 4 * 64, s, 2048);
+  }
+  expect_grid("the cap plus one group, statistics", 2048ull * 4 * 64 + 1, true, 2048);
+  expect_grid("the cap plus one group", 2048ull * 4 * 64 + 1, false, 2049);
+  expect_grid("the walking-wave tests' batch, statistics", (2 * 8192 + 2) * 64ull + 21, true, 2048);
+  expect_grid("the same without", (2 * 8192 + 2) * 64ull + 21, false, 4097);
+  // 2^31 - 1 blocks hold every batch of fewer than 2^39 groups
+  expect_grid("largest grid", 0x7FFFFFFFull * 256, false, 0x7FFFFFFFu);
+  expect_grid("past it", 0x7FFFFFFFull * 256 + 1, false, 0x7FFFFFFFu);
+}
+
 int main() {
+  tile_grid_cases();
   for (int fl = 0; fl < 2; fl++) {
     const bool f = fl != 0;
     // automatic chunk (override -1, and 0 = "persistent grid", which the

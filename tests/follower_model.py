@@ -20,6 +20,8 @@ import copy
 
 import numpy as np
 
+from tests.tick_model import mix64 as mix64_np
+
 M64 = (1 << 64) - 1
 NONE_SLOT = 0xFF
 
@@ -282,6 +284,23 @@ def group_stats(gid, before, after, out):
     h = mix64(h ^ after.last_index())
     s[STAT_CHECKSUM] = h
     return s
+
+
+def hash_chain(gid, salt, result, words):
+    """The checksum term of group_stats over arrays of groups (uint64,
+    wrapping): mix64 of the group id, the salt and the result, then one mix64
+    per state word."""
+    u64 = lambda a: np.asarray(a).astype(np.uint64)  # noqa: E731
+    with np.errstate(over="ignore"):
+        h = mix64_np((u64(gid) * np.uint64(PHI)) ^ np.uint64(salt) ^ (u64(result) << np.uint64(56)))
+        for w in words:
+            h = mix64_np(h ^ u64(w))
+    return h
+
+
+def group_hashes(gid, result, term, committed, last_index):
+    """group_stats' STAT_CHECKSUM, vectorised (the state words are the ones after the step)."""
+    return hash_chain(gid, FOLLOW_SALT, result, (term, committed, last_index))
 
 
 # ---------------------------------------------------------------------------

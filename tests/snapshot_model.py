@@ -260,6 +260,11 @@ def step_stats(gid, before, after, out):
     return s
 
 
+def step_hashes(gid, result, term, committed, last_index):
+    """step_stats' STAT_CHECKSUM, vectorised (the state words are the ones after the step)."""
+    return fm.hash_chain(gid, SNAP_SALT, result, (term, committed, last_index))
+
+
 def step_batch(nodes, msgs, num_slots, log_runs, group_offset=0):
     after, outs, stats = [], [], {}
     for g, (sn, m) in enumerate(zip(nodes, msgs)):
@@ -336,6 +341,12 @@ def compact_stats(gid, after, out, have_snap=True):
     h = mix64(h ^ (after.snap_index if have_snap else 0))
     s[STAT_CHECKSUM] = h
     return s
+
+
+def compact_hashes(gid, result, dummy_index, run_count, snap_index):
+    """compact_stats' STAT_CHECKSUM, vectorised: the dummy entry's index, the
+    run count and the snapshot index (0 without the row) after the call."""
+    return fm.hash_chain(gid, COMPACT_SALT, result, (dummy_index, run_count, snap_index))
 
 
 def compact_batch(nodes, reqs, group_offset=0, have_snap=True):

@@ -353,3 +353,56 @@ def test_events_feed_the_tick(eng):
     np.testing.assert_array_equal(out.events.cpu().numpy(), np.where(heard, fm.TEV_HEARD, 0))
     act = eng.tick(ps, t, events=out.events).action.cpu().numpy()
     np.testing.assert_array_equal(act & 1, np.where(heard, 0, 1))  # QE_TICK_HUP
+
+
+def test_walking_waves(eng):
+    """One launch in which every wave walks two or three tiles (tests/walk.py):
+    the base's 209 groups repeated, statistics on, a group offset past 2^32
+    and a stride that is no multiple of 64.  Every row is the base's
+    expectation repeated, every counter the repeated base's sum."""
+    from tests import walk
+    R, S, E = walk.R, walk.S, walk.E
+    b = walk.follower_base()
+    G = walk.walk_groups(torch.cuda.get_device_properties(DEV).multi_processor_count)
+    stride, idx = G + walk.PAD, np.arange(G) % walk.PERIOD
+    runs = {"run_first": R, "run_term": R}
+    a = walk.repeat(fm.pack_nodes(b.nodes, R, walk.PERIOD), G, stride, runs, fill=SENT)
+    ps = eng.ProgressState(G, S, 1, R, DEV, stride=stride, group_offset=walk.GOFF,
+                           extras=("lead_transferee",))
+    ps.load_host(**{k: a[k] for k in ("committed", "last_index", "run_first", "run_term",
+                                      "run_count", "lead_transferee")})
+    fol = eng.Follower(ps, check_quorum=bool(b.flags & 1), prevote=bool(b.flags & 2))
+    fol.load_host(**{k: a[k] for k in ("term", "state", "lead", "vote")})
+    lm = eng.LeaderMsgs(ps, E)
+    lm.load_host(**walk.repeat(fm.pack_msgs(b.msgs, E, walk.PERIOD), G, stride,
+                               {"ent_len": E, "ent_term": E}))
+    out = eng.FollowerOut(ps)
+    for k in OUT64:
+        getattr(out, k).fill_(SENT)
+    out.result.fill_(S8)
+    out.events.fill_(S8)
+    st = eng.stats_buffer(DEV)
+    eng.follower_step(ps, fol, lm, out, st)
+    want = walk.repeat(fm.pack_nodes(b.after, R, walk.PERIOD), G, stride, runs, fill=SENT)
+    u64 = lambda t: t.cpu().numpy().view(np.uint64)  # noqa: E731
+    got = {"committed": u64(ps.committed), "last_index": u64(ps.last_index),
+           "run_count": ps.run_count.cpu().numpy(),
+           "lead_transferee": ps.lead_transferee.cpu().numpy(), **fol.host()}
+    for k in SCALARS:
+        np.testing.assert_array_equal(got[k], want[k], err_msg=k)
+    live = np.arange(R)[:, None] < want["run_count"].astype(np.int64)[None, :]
+    for k in runs:
+        g2, w2 = u64(getattr(ps, k)).reshape(R, stride), want[k].reshape(R, stride)
+        np.testing.assert_array_equal(g2[:, :G][live], w2[:, :G][live], err_msg=k)
+        np.testing.assert_array_equal(g2[:, G:], w2[:, G:], err_msg=k + " pad")
+    o = out.host()
+    res = np.array([x["result"] for x in b.outs], np.uint8)[idx]
+    np.testing.assert_array_equal(o["result"], res, err_msg="result")
+    np.testing.assert_array_equal(o["events"], np.array([x["events"] for x in b.outs])[idx])
+    for k in OUT64:
+        np.testing.assert_array_equal(
+            o[k], np.array([x.get(k, SENT) for x in b.outs], np.uint64)[idx], err_msg=k)
+    folded = eng.stats_reduce(st).cpu().numpy().view(np.uint64)
+    ws = walk.expect_stats(b.shares, G, walk.follower_hashes(want, res))
+    np.testing.assert_array_equal(folded, ws, err_msg="stats")
+    assert ws[fm.STAT_GROUPS] > 0.8 * G and ws[fm.STAT_APPENDED] and ws[fm.STAT_COMMIT_ADVANCED]

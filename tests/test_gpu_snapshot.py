@@ -487,3 +487,111 @@ def test_runs_full_then_compact_then_accept(eng):
     assert (rf[0, :G] == 3).all() and (rt[0, :G] == 3).all()
     assert (rf[1, :G] == 4).all() and (rt[1, :G] == 4).all()
     np.testing.assert_array_equal(u64(h.ps.last_index), np.full(G, 4, np.uint64))
+
+
+def walk_state(eng, base_nodes):
+    """The base's SNodes repeated (tests/walk.py) and resident -> (ps, fol,
+    conf, G, stride)."""
+    from tests import walk
+    R, S = walk.R, walk.S
+    G = walk.walk_groups(torch.cuda.get_device_properties(DEV).multi_processor_count)
+    stride = G + walk.PAD
+    a = walk.repeat(sm.pack_snodes(base_nodes, R, S, walk.PERIOD), G, stride, walk_rows(G),
+                    fill=SENT)
+    ps = eng.ProgressState(G, S, 1, R, DEV, stride=stride, group_offset=walk.GOFF,
+                           extras=("self_slot", "lead_transferee", "snap_index"))
+    ps.load_host(**{k: a[k] for k in LOG + ("run_first", "run_term")})
+    fol = eng.Follower(ps)
+    fol.load_host(**{k: a[k] for k in FOL})
+    cs = eng.ConfState(G, S, DEV)
+    cs.slot_ids.copy_(torch.from_numpy(a["c_slot_ids"].view(np.int64)).to(DEV))
+    for k in sm.CONF_MASKS:
+        getattr(cs, k).copy_(torch.from_numpy(a["c_" + k]))
+    cs.auto_leave.copy_(torch.from_numpy(a["c_auto_leave"]))
+    return ps, fol, cs, G, stride
+
+
+def walk_rows(G):
+    from tests import walk
+    return {"run_first": walk.R, "run_term": walk.R, "c_slot_ids": (walk.S, G)}
+
+
+def walk_compare(ps, fol, cs, G, stride, after_nodes):
+    """The resident state against the base's nodes after the call, repeated;
+    -> the expectation."""
+    from tests import walk
+    R, S = walk.R, walk.S
+    want = walk.repeat(sm.pack_snodes(after_nodes, R, S, walk.PERIOD), G, stride, walk_rows(G),
+                       fill=SENT)
+    got = {k: getattr(ps, k).cpu().numpy() for k in LOG}
+    for k in ("committed", "last_index", "first_index", "snap_index"):
+        got[k] = got[k].view(np.uint64)
+    got.update(fol.host())
+    for k in sm.CONF_MASKS:
+        got["c_" + k] = getattr(cs, k).cpu().numpy()
+    got["c_auto_leave"], got["c_slot_ids"] = cs.auto_leave.cpu().numpy(), u64(cs.slot_ids)
+    for k in LOG + FOL + CONF:
+        np.testing.assert_array_equal(got[k], want[k], err_msg=k)
+    live = np.arange(R)[:, None] < want["run_count"].astype(np.int64)[None, :]
+    for k in ("run_first", "run_term"):
+        g2, w2 = u64(getattr(ps, k)).reshape(R, stride), want[k].reshape(R, stride)
+        np.testing.assert_array_equal(g2[:, :G][live], w2[:, :G][live], err_msg=k)
+        np.testing.assert_array_equal(g2[:, G:], w2[:, G:], err_msg=k + " pad")
+    return want
+
+
+def test_snapshot_walking_waves(eng):
+    """One qe_snapshot_step in which every wave walks two or three tiles
+    (tests/walk.py): the base's 209 groups repeated, statistics on, a group
+    offset past 2^32 and a stride that is no multiple of 64.  Every row is the
+    base's expectation repeated, every counter the repeated base's sum."""
+    from tests import walk
+    b = walk.snap_base()
+    ps, fol, cs, G, stride = walk_state(eng, b.nodes)
+    idx = np.arange(G) % walk.PERIOD
+    smg = eng.SnapMsgs(ps, ids=True)
+    smg.load_host(**walk.repeat(sm.pack_smsgs(b.msgs, walk.S, walk.PERIOD), G, stride,
+                                {"cs_ids": walk.S}))
+    out = eng.SnapOut(ps)
+    out.resp_index.fill_(SENT)
+    out.result.fill_(S8)
+    out.events.fill_(S8)
+    st = eng.stats_buffer(DEV)
+    eng.snapshot_step(ps, fol, cs, smg, out, st)
+    want = walk_compare(ps, fol, cs, G, stride, b.after)
+    o = out.host()
+    res = np.array([x["result"] for x in b.outs], np.uint8)[idx]
+    np.testing.assert_array_equal(o["result"], res, err_msg="result")
+    np.testing.assert_array_equal(o["events"], np.array([x["events"] for x in b.outs])[idx])
+    np.testing.assert_array_equal(
+        o["resp_index"], np.array([x.get("resp_index", SENT) for x in b.outs], np.uint64)[idx])
+    folded = eng.stats_reduce(st).cpu().numpy().view(np.uint64)
+    ws = walk.expect_stats(b.shares, G, walk.snap_hashes(want, res))
+    np.testing.assert_array_equal(folded, ws, err_msg="stats")
+    assert ws[sm.STAT_GROUPS] > 0.6 * G and ws[sm.STAT_GRANTED] and ws[sm.STAT_COMMIT_ADVANCED]
+
+
+def test_compact_walking_waves(eng):
+    """The same shape through qe_compact."""
+    from tests import walk
+    b = walk.compact_base()
+    ps, fol, cs, G, stride = walk_state(eng, b.nodes)
+    idx = np.arange(G) % walk.PERIOD
+    cp = eng.Compaction(ps)
+    cp.load_host(compact_index=np.array([r[0] for r in b.reqs], np.uint64)[idx],
+                 create_index=np.array([r[1] for r in b.reqs], np.uint64)[idx],
+                 applied=np.array([r[2] for r in b.reqs], np.uint64)[idx])
+    cp.result.fill_(S8)
+    cp.snap_term.fill_(SENT)
+    st = eng.stats_buffer(DEV)
+    eng.compact(ps, cp, st)
+    want = walk_compare(ps, fol, cs, G, stride, b.after)
+    o = cp.host()
+    res = np.array([x["result"] for x in b.outs], np.uint8)[idx]
+    np.testing.assert_array_equal(o["result"], res, err_msg="result")
+    np.testing.assert_array_equal(
+        o["snap_term"], np.array([x.get("snap_term", SENT) for x in b.outs], np.uint64)[idx])
+    folded = eng.stats_reduce(st).cpu().numpy().view(np.uint64)
+    ws = walk.expect_stats(b.shares, G, walk.compact_hashes(want, res))
+    np.testing.assert_array_equal(folded, ws, err_msg="stats")
+    assert ws[sm.STAT_GROUPS] > 0.6 * G and ws[sm.STAT_COMPACTED]

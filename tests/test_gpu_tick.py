@@ -337,3 +337,44 @@ def test_tick_actions_compact(eng):  # noqa: F811
     mo = m.tick(None, out=tm.TickOut(m))
     same(act, mo.action, "action")
     assert 0 < len(groups) < G
+
+
+def test_tick_walking_waves(eng):  # noqa: F811
+    """One tick in which every wave walks two or three tiles (tests/walk.py):
+    statistics on, a group offset past 2^32, a stride that is no multiple of
+    64.  The state generator steps a group at a time, so the state is 209
+    groups repeated; the model is vectorised and runs at the full size, with
+    events of its own for every group."""
+    from tests import walk
+    S, masks = walk.S, ()
+    G = walk.walk_groups(torch.cuda.get_device_properties(DEV).multi_processor_count)
+    stride, idx = G + walk.PAD, np.arange(G) % walk.PERIOD
+    rng = np.random.default_rng(2095)
+    pb, m0 = make_case(rng, walk.PERIOD, S, masks, True)
+
+    def rows(a):
+        big = np.zeros((S, stride), a.dtype)
+        big[:, :G] = a.reshape(S, walk.PERIOD)[:, idx]
+        return big.reshape(-1)
+    m = tm.Model(G, S, ET, HT, True, seed=77, goff=walk.GOFF, stride=stride)
+    for k in ("state", "ee", "he", "rt", "no_campaign"):
+        getattr(m, k)[:] = getattr(m0, k)[idx]
+    m.peer, m.match, m.committed = rows(pb.pw), rows(pb.match), pb.committed[idx]
+    m.tracked = pb.tracked.astype(np.int64)[idx]
+    m.self_slot, m.lead_transferee = pb.self_slot[idx], pb.lead_transferee[idx]
+    m.read_head, m.read_count = pb.read_head[idx], pb.read_count[idx]
+    ps = eng.ProgressState(G, S, 1, 4, DEV, stride=stride, group_offset=walk.GOFF, extras=READS)
+    ps.peer.copy_(torch.from_numpy(m.peer.view(np.int32)))  # (the rings are not the tick's)
+    ps.load_host(match=m.match, committed=m.committed, tracked=m.tracked.astype(np.uint8),
+                 self_slot=m.self_slot, lead_transferee=m.lead_transferee,
+                 read_head=m.read_head, read_count=m.read_count)
+    t = eng.Timers(G, ET, HT, True, m.seed, DEV)
+    t.load_host(state=m.state, election_elapsed=m.ee, heartbeat_elapsed=m.he,
+                randomized_timeout=m.rt.astype(np.uint16), no_campaign=m.no_campaign)
+    r = rng.random(G)
+    events = np.where(r < 0.8, 0, np.where(r < 0.9, 1, np.where(r < 0.97, 2, 3))).astype(np.uint8)
+    peer = ps.peer.cpu().numpy().view(np.uint32)
+    out, stats = gpu_tick(eng, ps, t, events)
+    mo = m.tick(events, out=tm.TickOut(m, SENT))
+    assert_tick(ps, t, out, stats, m, mo, peer)
+    assert stats[tm.ST_GROUPS] == G and stats[tm.ST_ELECTIONS] and stats[tm.ST_STEPDOWNS]

@@ -571,3 +571,58 @@ def test_closed_loop(eng, C_, N, flags):
         lead = [i for i in range(N) if state[c * N + i] == vm.ST_LEADER]
         terms = {cl.h.nodes[c * N + i].term for i in lead}
         assert len(terms) == len(lead), (c, lead)
+
+
+def test_walking_waves(eng):
+    """One candidate-form launch in which every wave walks two or three tiles
+    (tests/walk.py): the base's 209 groups repeated, statistics on, a group
+    offset past 2^32 and a stride that is no multiple of 64.  Every row is the
+    base's expectation repeated, every counter the repeated base's sum."""
+    from tests import walk
+    R, S = walk.R, walk.S
+    b = walk.vote_base()
+    G = walk.walk_groups(torch.cuda.get_device_properties(DEV).multi_processor_count)
+    stride, idx = G + walk.PAD, np.arange(G) % walk.PERIOD
+    runs = {"run_first": R, "run_term": R}
+    a = walk.repeat(vm.pack_nodes(b.nodes, R, S, walk.PERIOD), G, stride, runs, fill=SENT)
+    ps = eng.ProgressState(G, S, 1, R, DEV, masks=("inc",), group_offset=walk.GOFF, stride=stride,
+                           extras=("lead_transferee", "self_slot", "tracked"))
+    ps.load_host(**{k: a[k] for k in ("committed", "last_index", "run_first", "run_term",
+                                      "run_count", "lead_transferee", "inc", "tracked",
+                                      "self_slot")})
+    fol = eng.Follower(ps)
+    fol.load_host(**{k: a[k] for k in ("term", "state", "lead", "vote")})
+    voter = eng.Voter(ps, check_quorum=bool(b.flags & 1), prevote=bool(b.flags & 2),
+                      election_timeout=b.et)
+    voter.timer = torch.from_numpy(a["timer"].view(np.int32)).to(DEV)
+    voter.no_campaign = torch.from_numpy(a["no_campaign"]).to(DEV)
+    voter.load_host(voted=a["voted"], granted=a["granted"])
+    vmsg = eng.VoteMsgs(ps)
+    vmsg.load_host(**walk.repeat(vm.pack_msgs(b.msgs), G, stride))
+    out = eng.VoteOut(ps)
+    for k in OUTS:
+        getattr(out, k).view(torch.uint8).fill_(S8)
+    st = eng.stats_buffer(DEV)
+    log_before = {k: getattr(ps, k).clone() for k in ("run_first", "run_term") + LOG}
+    eng.vote_step(ps, fol, voter, vmsg, out, st)
+    want = walk.repeat(vm.pack_nodes(b.after, R, S, walk.PERIOD), G, stride, runs, fill=SENT)
+    got = {"term": _np(fol.term), "state": _np(fol.state), "lead": _np(fol.lead),
+           "vote": _np(fol.vote), "lead_transferee": _np(ps.lead_transferee),
+           "voted": _np(voter.voted), "granted": _np(voter.granted)}
+    for k in STATE:
+        np.testing.assert_array_equal(got[k], want[k], err_msg=k)
+    for k, v in log_before.items():  # the log is read only
+        assert torch.equal(getattr(ps, k), v), k
+    o = out.host()
+    res = np.array([x["result"] for x in b.outs], np.uint8)[idx]
+    ev = np.array([x["events"] for x in b.outs], np.uint8)[idx]
+    np.testing.assert_array_equal(o["result"], res, err_msg="result")
+    np.testing.assert_array_equal(o["events"], ev, err_msg="events")
+    np.testing.assert_array_equal(o["elected"], np.array([x["elected"] for x in b.outs])[idx])
+    for k, sent in (("resp_term", SENT), ("req_log_term", SENT), ("req_to", S8)):
+        np.testing.assert_array_equal(
+            o[k], np.array([x.get(k, sent) for x in b.outs], o[k].dtype)[idx], err_msg=k)
+    folded = eng.stats_reduce(st).cpu().numpy().view(np.uint64)
+    ws = walk.expect_stats(b.shares, G, walk.vote_hashes(want, res, ev))
+    np.testing.assert_array_equal(folded, ws, err_msg="stats")
+    assert ws[vm.STAT_GROUPS] > 0.8 * G and ws[vm.STAT_LEADERS] and ws[vm.STAT_STEPDOWNS]

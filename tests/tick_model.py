@@ -50,7 +50,10 @@ def draw(seed, gid, tick_no, et):
 
 def majority_vote(member, voted, granted):
     """MajorityConfig.VoteResult over slot bitmaps (majority.go:178-210)."""
-    pc = np.vectorize(lambda x: bin(int(x)).count("1"), otypes=[np.int64])
+    def pc(x):  # popcount of slot bitmaps (non-negative, below 2^32)
+        x = np.asarray(x, np.int64)
+        assert ((x >= 0) & (x < 1 << 32)).all()
+        return sum((x >> s) & 1 for s in range(32))
     n = pc(member)
     yes = pc(member & voted & granted)
     no = pc(member & voted & ~granted)

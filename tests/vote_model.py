@@ -303,6 +303,15 @@ def group_stats(gid, after, out, cand=True):
     return s
 
 
+def group_hashes(gid, result, term, state, lead, vote, events, voted, granted, cand=True):
+    """group_stats' STAT_CHECKSUM, vectorised (the state words are the ones after the step)."""
+    u64 = lambda a: np.asarray(a).astype(np.uint64)  # noqa: E731
+    head = u64(state) | u64(lead) << np.uint64(8) | u64(vote) << np.uint64(16) | \
+        u64(events) << np.uint64(24)
+    votes = (u64(voted) | u64(granted) << np.uint64(16)) if cand else np.uint64(0)
+    return fm.hash_chain(gid, VOTE_SALT, result, (term, head, votes))
+
+
 def step_batch(nodes, msgs, flags, num_slots, election_timeout=10, cand=True, have_self=True,
                group_offset=0):
     """-> (nodes after, outs, stats dict)"""
