@@ -240,6 +240,25 @@ class QeSnapOut(C.Structure):
     _fields_ = [("result", vp), ("resp_index", vp), ("events", vp)]
 
 
+# qe_outbox
+QE_OMSG_APP, QE_OMSG_SNAP, QE_OMSG_HEARTBEAT, QE_OMSG_BAD = 1, 2, 3, 255
+QE_STAT_OUTBOX_ENTRIES = 2    # = QE_STAT_COMMIT_SUM
+QE_STAT_OUTBOX_APP, QE_STAT_OUTBOX_SNAP, QE_STAT_OUTBOX_HEARTBEAT = 4, 5, 6  # = QE_STAT_VOTE_*
+QE_STAT_OUTBOX_BAD = 8        # = QE_STAT_REJECTED
+
+
+class QeOutboxIn(C.Structure):
+    _fields_ = [("sent", vp), ("snap", vp), ("hb_sent", vp), ("index", vp), ("next_before", vp),
+                ("term", vp), ("snap_term", vp), ("hb_commit", vp), ("hb_ctx", vp),
+                ("max_entries", u32), ("reserved", u32)]
+
+
+class QeOutboxOut(C.Structure):
+    _fields_ = [("capacity", u64), ("msg_runs", u32), ("reserved", u32), ("group", vp),
+                ("to", vp), ("type", vp), ("term", vp), ("index", vp), ("log_term", vp),
+                ("commit", vp), ("ctx", vp), ("ent_len", vp), ("ent_term", vp), ("count", vp)]
+
+
 QE_BL_NONE, QE_BL_LEADER, QE_BL_NOT_MEMBER, QE_BL_RUNS_FULL = 0, 1, 2, 3
 QE_BL_BCAST = 1
 
@@ -318,6 +337,9 @@ PROTOTYPES = {
     "qe_stats_reduce": (C.c_int, [vp, vp, vp]),
     "qe_collect_scratch_bytes": (C.c_size_t, [u64]),
     "qe_collect": (C.c_int, [u64, u64, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "qe_outbox_scratch_bytes": (C.c_size_t, [u64]),
+    "qe_outbox": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeOutboxIn), C.POINTER(QeOutboxOut),
+                            vp, vp, vp]),
     "qe_gen_groups": (C.c_int, [C.POINTER(QeGroups), C.POINTER(QeGenParams), vp]),
     "qe_apply_append_resps": (C.c_int, [u64, u32, u64, vp, vp, u64, vp, vp, vp, vp, vp]),
     "qe_pack_confstate": (C.c_int, [C.POINTER(QeConfStateCSR), u32, vp, vp, vp, vp, vp, vp]),

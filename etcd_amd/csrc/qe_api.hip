@@ -10,6 +10,7 @@
 #include "qe_follow.hpp"
 #include "qe_vote.hpp"
 #include "qe_snap.hpp"
+#include "qe_outbox.hpp"
 
 namespace qe {
 
@@ -964,6 +965,80 @@ int qe_collect(uint64_t num_groups, uint64_t group_offset, const uint64_t *perm,
   hipLaunchKernelGGL(k_collect_scatter, dim3(static_cast<unsigned>(nb)), dim3(kBlock), 0, st, flags,
                      num_groups, vec, group_offset, perm, values, offsets, out_groups, out_values);
   return hip_status(hipGetLastError());
+}
+
+size_t qe_outbox_scratch_bytes(uint64_t num_groups) {
+  static_assert(kObChunk == kCollectChunk, "k_collect_scan's chunks");
+  return qe_collect_scratch_bytes(num_groups);
+}
+
+int qe_outbox(const qe_progress *p, const qe_outbox_in *in, const qe_outbox_out *out,
+              void *scratch,
+              uint64_t *stats, void *stream) {
+  const int rc = check_progress(p);
+  if (rc) return rc;
+  if (!in || !out || !out->count || !in->term) return QE_EINVAL;
+  if (in->reserved || out->reserved || p->reserved3) return QE_EINVAL;
+  if (missing_log_model(p)) return QE_EINVAL;
+  if (in->sent && !in->index && !in->next_before) return QE_EINVAL;
+  if (in->sent && !in->index && (!p->next || !p->peer)) return QE_EINVAL;  // next_before is used
+  if (in->snap && !p->snap_index && !p->first_index) return QE_EINVAL;
+  if (in->hb_sent && !in->hb_commit) return QE_EINVAL;
+  if (out->msg_runs > QE_MAX_MSG_RUNS || (out->msg_runs && (!out->ent_len || !out->ent_term)))
+    return QE_EINVAL;
+  if (out->capacity && (!out->group || !out->to || !out->type || !out->term || !out->index ||
+                        !out->log_term || !out->commit))
+    return QE_EINVAL;
+  if (p->num_groups && (!scratch || reinterpret_cast<uintptr_t>(scratch) % 8)) return QE_EINVAL;
+  const uint64_t nb = (p->num_groups + kObChunk - 1) / kObChunk;
+  if (nb > 0x7FFFFFFFull) return QE_ERANGE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (p->num_groups == 0) return hip_status(hipMemsetAsync(out->count, 0, sizeof(uint64_t), st));
+  OBArgs a{};
+  step_head(p, stats, a);
+  a.S = p->num_slots;
+  a.wide = p->num_slots > 8;
+  a.max_entries = in->max_entries;
+  a.nb = nb;
+  a.sent = in->sent;
+  a.snap = in->snap;
+  a.hb_sent = in->hb_sent;
+  a.committed = p->committed;
+  a.last_index = p->last_index;
+  a.run_first = p->run_first;
+  a.run_term = p->run_term;
+  a.run_count = p->run_count;
+  a.next = p->next;
+  a.peer = p->peer;
+  a.snap_src = p->snap_index ? p->snap_index : p->first_index;
+  a.snap_sub = p->snap_index ? 0 : 1;
+  a.index = in->index;
+  a.next_before = in->next_before;
+  a.term = in->term;
+  a.snap_term = in->snap_term;
+  a.hb_commit = in->hb_commit;
+  a.hb_ctx = in->hb_ctx;
+  a.cap = out->capacity;
+  a.o_group = out->group;
+  a.o_to = out->to;
+  a.o_type = out->type;
+  a.o_term = out->term;
+  a.o_index = out->index;
+  a.o_log_term = out->log_term;
+  a.o_commit = out->commit;
+  a.o_ctx = out->ctx;
+  a.o_ent_len = out->ent_len;
+  a.o_ent_term = out->ent_term;
+  // scratch: offsets (u64, 8-B aligned at the start), then counts (u32), as qe_collect
+  uint64_t *offsets = static_cast<uint64_t *>(scratch);
+  a.offsets = offsets;
+  a.counts = reinterpret_cast<uint32_t *>(offsets + nb);
+  int s = dispatch_outbox_count(a, st);
+  if (s) return s;
+  hipLaunchKernelGGL(k_collect_scan, dim3(1), dim3(1024), 0, st, a.counts, nb, offsets, out->count);
+  s = hip_status(hipGetLastError());
+  if (s) return s;
+  return dispatch_outbox_fill(a, out->msg_runs, st);
 }
 
 int qe_stats_reduce(const uint64_t *stats, uint64_t *out, void *stream) {

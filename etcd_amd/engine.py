@@ -1100,6 +1100,74 @@ def snapshot_step(ps, fol, conf, msgs, out=None, stats=None):
     return out
 
 
+class Outbox(_Rows):
+    """The record arrays of qe_outbox (qe_outbox_out) for up to `capacity`
+    messages: group / term / index / log_term / commit int64 storage of the u64
+    fields, to / type u8 (QE_OMSG_*), ctx int32, the entries of a MsgApp as
+    msg_runs term runs ent_len int32 [E][capacity] / ent_term int64
+    [E][capacity], and `count` (int64[1]): the records the masks asked for,
+    which may exceed capacity.  The scratch of the call is cached here."""
+
+    FIELDS = ("group:u64 to:u8 type:u8 term:u64 index:u64 log_term:u64 commit:u64 ctx:u32 "
+              "ent_len:u32? ent_term:u64? count:u64")
+
+    def __init__(self, ps, capacity, msg_runs=_lib.QE_MAX_MSG_RUNS):
+        if not 0 <= int(msg_runs) <= _lib.QE_MAX_MSG_RUNS:
+            raise ValueError("msg_runs must be 0..QE_MAX_MSG_RUNS")
+        dev, i64, u8 = ps.device, torch.int64, torch.uint8
+        self.capacity, self.msg_runs = int(capacity), int(msg_runs)
+        n = max(1, self.capacity)
+        for k in ("group", "term", "index", "log_term", "commit"):
+            setattr(self, k, torch.zeros(n, dtype=i64, device=dev))
+        self.to = torch.zeros(n, dtype=u8, device=dev)
+        self.type = torch.zeros(n, dtype=u8, device=dev)
+        self.ctx = torch.zeros(n, dtype=torch.int32, device=dev)
+        e = self.msg_runs * n
+        self.ent_len = torch.zeros(e, dtype=torch.int32, device=dev) if e else None
+        self.ent_term = torch.zeros(e, dtype=i64, device=dev) if e else None
+        self.count = torch.zeros(1, dtype=i64, device=dev)
+        self.scratch = None
+
+    def struct(self):
+        return _lib.QeOutboxOut(self.capacity, self.msg_runs, 0, _ptr(self.group), _ptr(self.to),
+                                _ptr(self.type), _ptr(self.term), _ptr(self.index),
+                                _ptr(self.log_term), _ptr(self.commit), _ptr(self.ctx),
+                                _ptr(self.ent_len), _ptr(self.ent_term), _ptr(self.count))
+
+    def records(self):
+        """-> (count, the rows cut to min(count, capacity) as numpy arrays;
+        ent_len / ent_term as [E][n])."""
+        count = int(self.count.item())
+        n, cap = min(count, self.capacity), max(1, self.capacity)
+        h = self.host()
+        out = {k: h[k][:n] for k in self.ARRAYS if k not in ("ent_len", "ent_term", "count")}
+        for k in ("ent_len", "ent_term"):
+            out[k] = None if h[k] is None else h[k].reshape(self.msg_runs, cap)[:, :n]
+        return count, out
+
+
+def outbox(ps, term, ob, sent=None, snap=None, index=None, next_before=None, hb_sent=None,
+           hb_commit=None, hb_ctx=None, snap_term=None, max_entries=0, stats=None):
+    """qe_outbox: the masks of one leader-side call (sent / snap of
+    progress_step, propose, become_leader, progress_send, switch_config;
+    hb_sent of tick / heartbeat) -> the messages as a dense list in `ob`, in
+    (tile, slot, group) order.  `term` is the sender's term row (Follower.term).
+    m.Index comes from `index` (PeerMsgs.msg_index) or, for the calls that
+    report none, from `next_before` (a clone of ps.next taken before the call;
+    ps.next itself after become_leader).  Nothing of `ps` is written."""
+    lib = _lib.lib()
+    if ob.scratch is None:
+        ob.scratch = torch.empty((lib.qe_outbox_scratch_bytes(ps.G) + 7) // 8 + 1,
+                                 dtype=torch.int64, device=ps.device)
+    p, o = ps.struct(), ob.struct()
+    i = _lib.QeOutboxIn(_ptr(sent), _ptr(snap), _ptr(hb_sent), _ptr(index), _ptr(next_before),
+                        _ptr(term), _ptr(snap_term), _ptr(hb_commit), _ptr(hb_ctx),
+                        int(max_entries), 0)
+    check("qe_outbox", lib.qe_outbox(C.byref(p), C.byref(i), C.byref(o), _ptr(ob.scratch),
+                                     _ptr(stats), _stream(ps.device)))
+    return ob
+
+
 class Proposals:
     """One MsgProp per group for qe_propose (qe_proposals, ABI 6):
     num_entries [G] (0 = none), payload [G] (sum of the non-conf-change

@@ -529,6 +529,11 @@ typedef struct qe_peer_msgs {
  * qe_progress_send.  Messages from untracked slots are dropped.  An accept
  * with index > lastIndex is processed as the reference does and counted as
  * an invariant violation.
+ * The sends are reported as masks (sent, snap) and msg_index, not as messages.
+ * Building MsgApp{Index, LogTerm, Entries, Commit} / MsgSnap from them used to
+ * be a host duty for every leader-side entry point (walk the run table of the
+ * group for every set bit); it is optional now: qe_outbox lists the messages
+ * of one call's masks on the device.
  * qe_peer_msgs carries no term: raft.Step's preamble (raft.go:849-920) for
  * these messages is the HOST's.  Only a response of the group's own term,
  * received while the group leads, belongs here; a lower term is dropped, a
@@ -1626,6 +1631,127 @@ size_t qe_collect_scratch_bytes(uint64_t num_groups);
 int qe_collect(uint64_t num_groups, uint64_t group_offset, const uint64_t *perm,
                const uint8_t *flags, const uint64_t *values, uint64_t *out_groups,
                uint64_t *out_values, uint64_t *out_count, void *scratch, void *stream);
+
+/* qe_outbox (additive in ABI 8): the messages one leader-side call sent, as a
+ * dense, ordered list of records on the device -- the Ready.Messages half of
+ * the Ready whose commit half qe_collect lists.  The step entry points report
+ * a send as mask bits (`sent`, `snap`, `hb_sent`) and a few rows (msg_index,
+ * hb_commit, hb_ctx); this call turns the masks of ONE call into
+ * MsgApp{Index, LogTerm, Entries, Commit} (maybeSendAppend, raft/raft.go:
+ * 432-492: Index = pr.Next - 1, LogTerm = term(Index), the entries after it,
+ * Commit = raftLog.committed; the MsgSnap arm with the snapshot's Metadata)
+ * and MsgHeartbeat{Commit, Context} (sendHeartbeat / bcastHeartbeatWithCtx,
+ * :495-532) records.  It READS the resident state of p and never writes it;
+ * of p it reads num_groups, group_offset, num_slots, stride, log_runs,
+ * committed, last_index, run_first, run_term, run_count and, by need, next,
+ * peer, snap_index and first_index.
+ *
+ *  1. Mask.  Per group mask = (sent | snap | hb_sent) & ((1 << num_slots) - 1),
+ *     a NULL mask array taken as 0.  Every set bit s yields exactly one record,
+ *     of type QE_OMSG_SNAP where the snap bit is set, else QE_OMSG_APP where
+ *     the sent bit is set, else QE_OMSG_HEARTBEAT.  The masks are those of one
+ *     call (qe_progress_step's sent / snap, qe_tick's hb_sent, ...).
+ *  2. Order.  Records are listed by ascending tile (g / 64), then slot, then g.
+ *     The order is part of the contract; *count depends on the masks alone.
+ *  3. Truncation.  A record at a position >= capacity is not written; *count
+ *     is still the full number, and nothing at or past min(*count, capacity)
+ *     is touched in any output array.
+ *  4. QE_OMSG_APP.  index = in->index[s*stride+g] when `index` is given (the
+ *     msg_index row of qe_progress_step).  Otherwise, for the entry points
+ *     that report no index (qe_propose, qe_become_leader, qe_progress_send,
+ *     qe_switch_config): next_before[s*stride+g] - 1 for a peer whose peer
+ *     word says QE_PR_REPLICATE after the call (an optimistic send moved Next
+ *     past the message, :468-477), p->next[s*stride+g] - 1 for every other
+ *     state (a probe leaves Next alone); next_before is a copy of p->next
+ *     taken before the call (p->next itself after qe_become_leader, where
+ *     every peer probes).  With r0 = run_first[0]: an index outside
+ *     [r0, last_index] (or a group with run_count 0) gives type QE_OMSG_BAD
+ *     with `index` as computed and log_term, commit, ctx and the entry runs 0.
+ *     Otherwise log_term = term(index) on the run table (raftLog.term),
+ *     commit = committed[g], and the entries are (index, hi] with hi =
+ *     min(last_index, index + (max_entries ? max_entries : 0xFFFFFFFF)), split
+ *     into the term runs of the table: run j of the message is the j-th table
+ *     run that overlaps (index, hi], ent_len[j*capacity+i] its overlap and
+ *     ent_term[j*capacity+i] its term.  The message is cut after msg_runs
+ *     runs: it then ends where its last listed run ends (with msg_runs 0 no
+ *     entries are listed).  Unused ent_len / ent_term rows of a record are 0.
+ *  5. QE_OMSG_SNAP.  index = snap_index[g] (first_index[g] - 1 when
+ *     p->snap_index is NULL), log_term = in->snap_term[g], or term(index) on
+ *     the run table (0 outside the log) when in->snap_term is NULL; commit 0,
+ *     no runs.  The ConfState is not in the record: it belongs to the
+ *     snapshot the application stored (Storage.Snapshot()), as for
+ *     qe_snapshot_step's inputs.
+ *  6. QE_OMSG_HEARTBEAT.  commit = hb_commit[s*stride+g], ctx = hb_ctx[g] (0
+ *     with hb_ctx NULL); index and log_term 0, no runs.
+ *  7. Every record, QE_OMSG_BAD included: group = group_offset + g, to = s,
+ *     term = in->term[g] (the sender's r.Term); ctx is 0 for every type but
+ *     the heartbeat.
+ *  8. stats (optional), over every record the masks ask for, those past
+ *     capacity too: QE_STAT_GROUPS += groups with a non-empty mask;
+ *     QE_STAT_OUTBOX_APP / _SNAP / _HEARTBEAT / _BAD += records by type, BAD
+ *     also into QE_STAT_INVARIANT_VIOLATIONS; QE_STAT_OUTBOX_ENTRIES += entries
+ *     listed (the sum of a record's ent_len); QE_STAT_CHECKSUM += h5 per
+ *     record, h1 = mix64((group_offset + g) * 0x9E3779B97F4A7C15 ^
+ *     0xC2B2AE3D27D4EB4F ^ type << 56 ^ to << 48), h2 = mix64(h1 ^ index), h3 =
+ *     mix64(h2 ^ log_term), h4 = mix64(h3 ^ commit), h5 = mix64(h4 ^ entries
+ *     listed).
+ * `count` and every array of qe_outbox_out are DEVICE pointers; scratch is
+ * qe_outbox_scratch_bytes(num_groups) bytes of device memory, 8-B aligned.
+ * Stream-ordered: three kernels (count per 4096-group chunk, the scan of
+ * qe_collect, fill), no host synchronisation.
+ * QE_EINVAL: a NULL p / in / out / scratch (with num_groups > 0) / count /
+ * term; a NULL committed, last_index, run_first, run_term or run_count;
+ * log_runs 0 or > QE_MAX_LOG_RUNS; stride < num_groups; `sent` given with
+ * neither `index` nor `next_before`; next_before used (index NULL) with a NULL
+ * p->next or p->peer; `snap` given with p->snap_index and p->first_index both
+ * NULL; hb_sent without hb_commit; msg_runs > QE_MAX_MSG_RUNS, or > 0 without
+ * ent_len / ent_term; capacity > 0 with a NULL group / to / type / term /
+ * index / log_term / commit array (ctx may be NULL: not written); a nonzero
+ * reserved field; scratch not 8-B aligned.  Every argument check runs before
+ * the first HIP call.  num_groups == 0 is QE_OK with *count = 0.
+ *
+ * With this call duty H7 of a host (tests/cluster_sim.py: pick m.Index, look
+ * up LogTerm, cut the entries into term runs, attach Commit and Term) is
+ * optional: the host copies min(*count, capacity) records instead of the
+ * G-sized and S x stride-sized rows it would walk. */
+#define QE_OMSG_APP 1        /* MsgApp       */
+#define QE_OMSG_SNAP 2       /* MsgSnap: index / log_term = Metadata.Index / Term */
+#define QE_OMSG_HEARTBEAT 3  /* MsgHeartbeat */
+#define QE_OMSG_BAD 255      /* a mask bit whose m.Index is outside the log */
+#define QE_STAT_OUTBOX_ENTRIES QE_STAT_COMMIT_SUM    /* qe_outbox: entries listed */
+#define QE_STAT_OUTBOX_APP QE_STAT_VOTE_WON          /* ... records by type */
+#define QE_STAT_OUTBOX_SNAP QE_STAT_VOTE_LOST
+#define QE_STAT_OUTBOX_HEARTBEAT QE_STAT_VOTE_PENDING
+#define QE_STAT_OUTBOX_BAD QE_STAT_REJECTED
+
+typedef struct qe_outbox_in {
+  const void *sent, *snap, *hb_sent;   /* [G] mask-typed, each may be NULL */
+  const uint64_t *index;        /* [S][stride] m.Index (qe_peer_msgs.msg_index), or NULL */
+  const uint64_t *next_before;  /* [S][stride] Next as it was before the call, or NULL */
+  const uint64_t *term;         /* [G] the sender's r.Term (qe_follower.term), required */
+  const uint64_t *snap_term;    /* [G] or NULL: NULL = term(snap_index) from the runs */
+  const uint64_t *hb_commit;    /* [S][stride], required with hb_sent */
+  const uint32_t *hb_ctx;       /* [G] or NULL (ctx 0) */
+  uint32_t max_entries;         /* entries per MsgApp at most, 0 = no limit */
+  uint32_t reserved;            /* must be 0 */
+} qe_outbox_in;
+
+typedef struct qe_outbox_out {
+  uint64_t capacity;            /* records the arrays hold */
+  uint32_t msg_runs;            /* E, 0..QE_MAX_MSG_RUNS */
+  uint32_t reserved;
+  uint64_t *group;              /* [capacity] group_offset + g */
+  uint8_t  *to, *type;          /* [capacity] slot, QE_OMSG_* */
+  uint64_t *term, *index, *log_term, *commit;  /* [capacity] */
+  uint32_t *ctx;                /* [capacity] or NULL */
+  uint32_t *ent_len;            /* [E][capacity] */
+  uint64_t *ent_term;           /* [E][capacity] */
+  uint64_t *count;              /* device: records the masks ask for (may exceed capacity) */
+} qe_outbox_out;
+
+size_t qe_outbox_scratch_bytes(uint64_t num_groups);
+int qe_outbox(const qe_progress *p, const qe_outbox_in *in, const qe_outbox_out *out,
+              void *scratch, uint64_t *stats, void *stream);
 
 /* ---- statistics -------------------------------------------------------- */
 
