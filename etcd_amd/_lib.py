@@ -259,6 +259,38 @@ class QeOutboxOut(C.Structure):
                 ("commit", vp), ("ctx", vp), ("ent_len", vp), ("ent_term", vp), ("count", vp)]
 
 
+# qe_inbox
+QE_IMSG_APP, QE_IMSG_SNAP, QE_IMSG_HEARTBEAT = 1, 2, 3   # = QE_OMSG_*
+(QE_IMSG_APP_RESP, QE_IMSG_APP_RESP_REJECT, QE_IMSG_HEARTBEAT_RESP, QE_IMSG_SNAP_STATUS,
+ QE_IMSG_SNAP_STATUS_REJECT, QE_IMSG_UNREACHABLE, QE_IMSG_TRANSFER_LEADER) = range(4, 11)
+(QE_IMSG_VOTE, QE_IMSG_PREVOTE, QE_IMSG_VOTE_RESP, QE_IMSG_PREVOTE_RESP, QE_IMSG_TIMEOUT_NOW,
+ QE_IMSG_HUP) = range(11, 17)
+(QE_ID_ROUTED, QE_ID_STEPDOWN, QE_ID_DEFERRED, QE_ID_DROP_LOWER_TERM,
+ QE_ID_DROP_NOT_LEADER) = range(1, 6)
+QE_ID_BAD = 255
+QE_INBOX_SRC_TICK = 0xFFFFFFFF
+QE_STAT_INBOX_BAD = 1          # = QE_STAT_COMMIT_INF
+QE_STAT_INBOX_ROUTED, QE_STAT_INBOX_LOWER_TERM, QE_STAT_INBOX_DEFERRED = 4, 5, 6  # = QE_STAT_VOTE_*
+QE_STAT_INBOX_NOT_LEADER = 8   # = QE_STAT_REJECTED
+QE_STAT_INBOX_STEPDOWN = 13    # = QE_STAT_STEPDOWNS
+
+
+class QeInboxIn(C.Structure):
+    _fields_ = [("num_records", u64), ("msg_runs", u32), ("reserved", u32), ("group", vp),
+                ("from_", vp), ("type", vp), ("term", vp), ("index", vp), ("log_term", vp),
+                ("commit", vp), ("hint", vp), ("ctx", vp), ("flags", vp), ("ent_len", vp),
+                ("ent_term", vp), ("tick_action", vp)]
+
+
+class QeInboxOut(C.Structure):
+    _fields_ = [(k, vp) for k in (
+        "f_type", "f_from", "f_term", "f_index", "f_log_term", "f_commit", "f_ent_len",
+        "f_ent_term", "s_type", "s_from", "s_term", "s_snap_index", "s_snap_term", "v_type",
+        "v_from", "v_term", "v_index", "v_log_term", "v_flags", "r_type", "r_index", "r_hint",
+        "r_log_term", "r_ctx", "f_src", "s_src", "v_src", "r_src", "disposition", "deferred",
+        "deferred_count")]
+
+
 QE_BL_NONE, QE_BL_LEADER, QE_BL_NOT_MEMBER, QE_BL_RUNS_FULL = 0, 1, 2, 3
 QE_BL_BCAST = 1
 
@@ -340,6 +372,9 @@ PROTOTYPES = {
     "qe_outbox_scratch_bytes": (C.c_size_t, [u64]),
     "qe_outbox": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeOutboxIn), C.POINTER(QeOutboxOut),
                             vp, vp, vp]),
+    "qe_inbox_scratch_bytes": (C.c_size_t, [u64, u32, u64]),
+    "qe_inbox": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeFollower), C.POINTER(QeInboxIn),
+                           C.POINTER(QeInboxOut), vp, vp, vp]),
     "qe_gen_groups": (C.c_int, [C.POINTER(QeGroups), C.POINTER(QeGenParams), vp]),
     "qe_apply_append_resps": (C.c_int, [u64, u32, u64, vp, vp, u64, vp, vp, vp, vp, vp]),
     "qe_pack_confstate": (C.c_int, [C.POINTER(QeConfStateCSR), u32, vp, vp, vp, vp, vp, vp]),

@@ -11,6 +11,7 @@
 #include "qe_vote.hpp"
 #include "qe_snap.hpp"
 #include "qe_outbox.hpp"
+#include "qe_inbox.hpp"
 
 namespace qe {
 
@@ -1039,6 +1040,120 @@ int qe_outbox(const qe_progress *p, const qe_outbox_in *in, const qe_outbox_out 
   s = hip_status(hipGetLastError());
   if (s) return s;
   return dispatch_outbox_fill(a, out->msg_runs, st);
+}
+
+size_t qe_inbox_scratch_bytes(uint64_t num_groups, uint32_t num_slots, uint64_t num_records) {
+  static_assert(kIbChunk == kCollectChunk, "k_collect_count's and k_collect_scan's chunks");
+  if (num_slots == 0 || num_slots > QE_MAX_SLOTS) return 0;
+  return static_cast<size_t>(4 * (3 + static_cast<uint64_t>(num_slots)) * num_groups +
+                             num_records + qe_collect_scratch_bytes(num_records));
+}
+
+int qe_inbox(const qe_progress *p, const qe_follower *f, const qe_inbox_in *in,
+             const qe_inbox_out *out, void *scratch, uint64_t *stats, void *stream) {
+  const int rc = check_progress(p);
+  if (rc) return rc;
+  if (!f || !in || !out || !f->term || !f->state) return QE_EINVAL;
+  if (in->reserved) return QE_EINVAL;
+  if (p->num_groups && p->stride < p->num_groups) return QE_EINVAL;
+  if (in->msg_runs > QE_MAX_MSG_RUNS ||
+      (in->msg_runs && (!in->ent_len || !in->ent_term || !out->f_ent_len || !out->f_ent_term)))
+    return QE_EINVAL;
+  const uint64_t n = in->num_records;
+  if (n && (!in->group || !in->from || !in->type || !in->term || !in->index || !in->log_term ||
+            !in->commit || !in->hint))
+    return QE_EINVAL;
+  if (!out->f_type || !out->f_from || !out->f_term || !out->f_index || !out->f_log_term ||
+      !out->f_commit || !out->s_type || !out->s_from || !out->s_term || !out->s_snap_index ||
+      !out->s_snap_term || !out->v_type || !out->v_from || !out->v_term || !out->v_index ||
+      !out->v_log_term || !out->r_type || !out->r_index || !out->r_hint || !out->r_log_term ||
+      !out->disposition || !out->deferred || !out->deferred_count)
+    return QE_EINVAL;
+  if (p->num_groups && !scratch) return QE_EINVAL;
+  if (reinterpret_cast<uintptr_t>(scratch) % 8) return QE_EINVAL;
+  if (n > 0xFFFFFFF0ull) return QE_ERANGE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (p->num_groups == 0)
+    return hip_status(hipMemsetAsync(out->deferred_count, 0, sizeof(uint64_t), st));
+  IBArgs a{};
+  a.G = p->num_groups;
+  a.goff = p->group_offset;
+  a.stride = p->stride;
+  a.n = n;
+  a.S = p->num_slots;
+  a.E = in->msg_runs;
+  a.fterm = f->term;
+  a.fstate = f->state;
+  a.group = in->group;
+  a.from = in->from;
+  a.type = in->type;
+  a.term = in->term;
+  a.index = in->index;
+  a.log_term = in->log_term;
+  a.commit = in->commit;
+  a.hint = in->hint;
+  a.ctx = in->ctx;
+  a.flags = in->flags;
+  a.ent_len = in->ent_len;
+  a.ent_term = in->ent_term;
+  a.tick = in->tick_action;
+  a.f_type = out->f_type;
+  a.f_from = out->f_from;
+  a.f_term = out->f_term;
+  a.f_index = out->f_index;
+  a.f_log_term = out->f_log_term;
+  a.f_commit = out->f_commit;
+  a.f_ent_len = out->f_ent_len;
+  a.f_ent_term = out->f_ent_term;
+  a.s_type = out->s_type;
+  a.s_from = out->s_from;
+  a.s_term = out->s_term;
+  a.s_snap_index = out->s_snap_index;
+  a.s_snap_term = out->s_snap_term;
+  a.v_type = out->v_type;
+  a.v_from = out->v_from;
+  a.v_term = out->v_term;
+  a.v_index = out->v_index;
+  a.v_log_term = out->v_log_term;
+  a.v_flags = out->v_flags;
+  a.r_type = out->r_type;
+  a.r_index = out->r_index;
+  a.r_hint = out->r_hint;
+  a.r_log_term = out->r_log_term;
+  a.r_ctx = out->r_ctx;
+  a.f_src = out->f_src;
+  a.s_src = out->s_src;
+  a.v_src = out->v_src;
+  a.r_src = out->r_src;
+  a.disposition = out->disposition;
+  a.deferred = out->deferred;
+  a.stats = stats;
+  // scratch: qe_collect's part for n flags (offsets u64, 8-B aligned at the start, then counts
+  // u32), the words first / stop / hi [G] and cell [S][G], the flags [n]
+  const uint64_t nb = (n + kIbChunk - 1) / kIbChunk;
+  uint64_t *offsets = static_cast<uint64_t *>(scratch);
+  uint32_t *counts = reinterpret_cast<uint32_t *>(offsets + nb);
+  a.offsets = offsets;
+  a.first = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(scratch) +
+                                         qe_collect_scratch_bytes(n));
+  a.stop = a.first + a.G;
+  a.hi = a.stop + a.G;
+  a.cell = a.hi + a.G;
+  a.dflag = reinterpret_cast<uint8_t *>(a.cell + a.S * a.G);
+  int s = dispatch_inbox_init(a, st);
+  if (s) return s;
+  if (n) {
+    s = dispatch_inbox_passes(a, st);
+    if (s) return s;
+    const bool vec = (reinterpret_cast<uintptr_t>(a.dflag) % 16) == 0;
+    hipLaunchKernelGGL(k_collect_count, dim3(static_cast<unsigned>((nb + kCountWaves - 1) / kCountWaves)),
+                       dim3(kBlock), 0, st, a.dflag, n, vec, nb, counts);
+  }
+  hipLaunchKernelGGL(k_collect_scan, dim3(1), dim3(1024), 0, st, counts, nb, offsets,
+                     out->deferred_count);
+  s = hip_status(hipGetLastError());
+  if (s || !n) return s;
+  return dispatch_inbox_deferred(a, nb, st);
 }
 
 int qe_stats_reduce(const uint64_t *stats, uint64_t *out, void *stream) {

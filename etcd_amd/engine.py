@@ -1168,6 +1168,149 @@ def outbox(ps, term, ob, sent=None, snap=None, index=None, next_before=None, hb_
     return ob
 
 
+class Inbox(_Rows):
+    """The record list of qe_inbox (qe_inbox_in) for up to `capacity` delivered
+    messages, and the per-record outputs: group / term / index / log_term /
+    commit / hint int64 storage of the u64 fields, from_ / type (QE_IMSG_*) /
+    flags (QE_VMF_*) u8, ctx int32, the entries of a MsgApp as msg_runs term
+    runs ent_len int32 / ent_term int64 laid out [E][n] for the n records
+    loaded; `disposition` u8 (QE_ID_*), `deferred` int32 positions and
+    `deferred_count` (int64[1]).  With src=True it also holds the source
+    position rows f_src / s_src / v_src [G] and r_src [S][stride] (int32).
+    The scratch of the call is cached here."""
+
+    FIELDS = ("group:u64 from_:u8 type:u8 term:u64 index:u64 log_term:u64 commit:u64 hint:u64 "
+              "ctx:u32? flags:u8? ent_len:u32? ent_term:u64? disposition:u8 deferred:u32 "
+              "deferred_count:u64")
+    RECORD = ("group", "from_", "type", "term", "index", "log_term", "commit", "hint", "ctx",
+              "flags")
+
+    def __init__(self, ps, capacity, msg_runs=_lib.QE_MAX_MSG_RUNS, ctx=True, flags=True,
+                 src=True):
+        if not 0 <= int(msg_runs) <= _lib.QE_MAX_MSG_RUNS:
+            raise ValueError("msg_runs must be 0..QE_MAX_MSG_RUNS")
+        dev, i64, i32, u8 = ps.device, torch.int64, torch.int32, torch.uint8
+        self.capacity, self.msg_runs, self.n = int(capacity), int(msg_runs), 0
+        c = max(1, self.capacity)
+        for k in ("group", "term", "index", "log_term", "commit", "hint"):
+            setattr(self, k, torch.zeros(c, dtype=i64, device=dev))
+        self.from_ = torch.zeros(c, dtype=u8, device=dev)
+        self.type = torch.zeros(c, dtype=u8, device=dev)
+        self.ctx = torch.zeros(c, dtype=i32, device=dev) if ctx else None
+        self.flags = torch.zeros(c, dtype=u8, device=dev) if flags else None
+        e = self.msg_runs * c
+        self.ent_len = torch.zeros(e, dtype=i32, device=dev) if e else None
+        self.ent_term = torch.zeros(e, dtype=i64, device=dev) if e else None
+        self.disposition = torch.zeros(c, dtype=u8, device=dev)
+        self.deferred = torch.zeros(c, dtype=i32, device=dev)
+        self.deferred_count = torch.zeros(1, dtype=i64, device=dev)
+        self.f_src = self.s_src = self.v_src = self.r_src = None
+        if src:
+            self.f_src = torch.zeros(ps.G, dtype=i32, device=dev)
+            self.s_src = torch.zeros(ps.G, dtype=i32, device=dev)
+            self.v_src = torch.zeros(ps.G, dtype=i32, device=dev)
+            self.r_src = torch.zeros(ps.S * ps.stride, dtype=i32, device=dev)
+        self.scratch = None
+
+    def _put(self, n, after, rows, ents):
+        """Records after..n-1 from device tensors; the first `after` stay."""
+        if not 0 <= after <= self.n or n > self.capacity:
+            raise ValueError("the list does not fit the Inbox")
+        for k, t in rows.items():
+            dst = getattr(self, k)
+            if dst is not None:
+                dst[after:n].copy_(t)
+        E = self.msg_runs
+        for k, t in ents.items():
+            buf = getattr(self, k)
+            if buf is None:
+                continue
+            new = torch.zeros((E, n), dtype=buf.dtype, device=buf.device)
+            new[:, :after] = buf[: E * self.n].view(E, self.n)[:, :after]
+            new[:, after:] = t
+            buf[: E * n].copy_(new.view(-1))
+        self.n = n
+
+    def load_host(self, after=0, **arrays):
+        """The list from numpy arrays of the unsigned types (`from` is accepted
+        for `from_`): records `after`.. are replaced, the first `after` records
+        (a gathered deferred list) stay.  ent_len / ent_term are [E][m] for the
+        m records given; a field left out is 0."""
+        arrays = {("from_" if k == "from" else k): v for k, v in arrays.items()}
+        m = len(arrays["group"])
+        n, dev = after + m, self.group.device
+
+        def dev_of(k, shape):
+            dt = getattr(self, k).dtype
+            if k not in arrays:
+                return torch.zeros(shape, dtype=dt, device=dev)
+            a = np.ascontiguousarray(arrays[k])
+            a = a.view(_SIGNED.get(a.dtype, a.dtype)).reshape(shape)
+            return torch.from_numpy(a.copy()).to(dev).to(dt)
+
+        rows = {k: dev_of(k, (m,)) for k in self.RECORD if getattr(self, k) is not None}
+        ents = {k: dev_of(k, (self.msg_runs, m)) for k in ("ent_len", "ent_term")
+                if getattr(self, k) is not None}
+        self._put(n, after, rows, ents)
+        return self
+
+    def results(self):
+        """-> (disposition[n], the deferred positions, ascending) as numpy."""
+        count = int(self.deferred_count.item())
+        return (self.disposition[: self.n].cpu().numpy(),
+                self.deferred[:count].cpu().numpy().view(np.uint32))
+
+    def gather_deferred(self, out=None):
+        """The next pass's list: the DEFERRED records in list order, gathered on
+        the device into `out` (default: this Inbox); -> out, with out.n = their
+        number.  New arrivals go behind them with load_host(after=out.n, ...)."""
+        out = self if out is None else out
+        count = int(self.deferred_count.item())
+        idx = self.deferred[:count].to(torch.int64)
+        rows = {k: getattr(self, k)[idx] for k in self.RECORD
+                if getattr(self, k) is not None and getattr(out, k) is not None}
+        E = self.msg_runs
+        ents = {k: getattr(self, k)[: E * self.n].view(E, self.n)[:, idx]
+                for k in ("ent_len", "ent_term") if getattr(self, k) is not None}
+        out.n = 0
+        out._put(count, 0, rows, ents)
+        return out
+
+
+def inbox(ps, fol, ib, lm, sm, vm, pm, tick_action=None, stats=None):
+    """qe_inbox: the list of `ib` routed into the rows of the LeaderMsgs `lm`,
+    SnapMsgs `sm`, VoteMsgs `vm` and PeerMsgs `pm` (type / index / reject_hint /
+    log_term and, where pm.read_ctx is set, the heartbeat contexts), which then
+    go to follower_step, snapshot_step, progress_step and vote_step -- in that
+    order: progress_step before vote_step.  `tick_action` is a TickOut's action
+    row: its QE_TICK_HUP groups get a QE_VMSG_HUP.  The dispositions and the
+    deferred list are left in `ib` (results(), gather_deferred())."""
+    if lm.msg_runs != ib.msg_runs:
+        raise ValueError("the LeaderMsgs and the Inbox differ in msg_runs")
+    lib = _lib.lib()
+    need = lib.qe_inbox_scratch_bytes(ps.G, ps.S, ib.n)
+    if ib.scratch is None or ib.scratch.numel() * 8 < need:
+        grow = lib.qe_inbox_scratch_bytes(ps.G, ps.S, max(1, ib.capacity))
+        ib.scratch = torch.empty((max(need, grow) + 7) // 8 + 1, dtype=torch.int64,
+                                 device=ps.device)
+    p, f = ps.struct(), fol.struct()
+    i = _lib.QeInboxIn(ib.n, ib.msg_runs, 0, _ptr(ib.group), _ptr(ib.from_), _ptr(ib.type),
+                       _ptr(ib.term), _ptr(ib.index), _ptr(ib.log_term), _ptr(ib.commit),
+                       _ptr(ib.hint), _ptr(ib.ctx), _ptr(ib.flags), _ptr(ib.ent_len),
+                       _ptr(ib.ent_term), _ptr(tick_action))
+    o = _lib.QeInboxOut(
+        _ptr(lm.type), _ptr(lm.from_), _ptr(lm.term), _ptr(lm.index), _ptr(lm.log_term),
+        _ptr(lm.commit), _ptr(lm.ent_len), _ptr(lm.ent_term),
+        _ptr(sm.type), _ptr(sm.from_), _ptr(sm.term), _ptr(sm.snap_index), _ptr(sm.snap_term),
+        _ptr(vm.type), _ptr(vm.from_), _ptr(vm.term), _ptr(vm.index), _ptr(vm.log_term),
+        _ptr(vm.flags), _ptr(pm.type), _ptr(pm.index), _ptr(pm.reject_hint), _ptr(pm.log_term),
+        _ptr(pm.read_ctx), _ptr(ib.f_src), _ptr(ib.s_src), _ptr(ib.v_src), _ptr(ib.r_src),
+        _ptr(ib.disposition), _ptr(ib.deferred), _ptr(ib.deferred_count))
+    check("qe_inbox", lib.qe_inbox(C.byref(p), C.byref(f), C.byref(i), C.byref(o),
+                                   _ptr(ib.scratch), _ptr(stats), _stream(ps.device)))
+    return ib
+
+
 class Proposals:
     """One MsgProp per group for qe_propose (qe_proposals, ABI 6):
     num_entries [G] (0 = none), payload [G] (sum of the non-conf-change

@@ -535,7 +535,8 @@ typedef struct qe_peer_msgs {
  * group for every set bit); it is optional now: qe_outbox lists the messages
  * of one call's masks on the device.
  * qe_peer_msgs carries no term: raft.Step's preamble (raft.go:849-920) for
- * these messages is the HOST's.  Only a response of the group's own term,
+ * these messages is the HOST's (or qe_inbox's, which runs it on a list of
+ * delivered messages and fills these rows).  Only a response of the group's own term,
  * received while the group leads, belongs here; a lower term is dropped, a
  * group that does not lead has no arm for it, and a higher term goes to
  * qe_vote_step as a QE_VMSG_VOTE_RESP of that term with QE_VMF_REJECT
@@ -1752,6 +1753,182 @@ typedef struct qe_outbox_out {
 size_t qe_outbox_scratch_bytes(uint64_t num_groups);
 int qe_outbox(const qe_progress *p, const qe_outbox_in *in, const qe_outbox_out *out,
               void *scratch, uint64_t *stats, void *stream);
+
+/* qe_inbox (additive in ABI 8): a list of delivered messages routed into the
+ * message rows of the step entry points -- the receive half of the loop whose
+ * send half qe_outbox lists.  Every step entry point takes whole-batch rows
+ * with at most one message per group (qe_progress_step: one per slot and
+ * group); this call picks, per group, which records of the list go into this
+ * pass of calls and which wait, runs raft.Step's term preamble for the
+ * response types (qe_peer_msgs carries no term), turns a higher-term response
+ * into the QE_VMSG_VOTE_RESP qe_progress_step's comment asks for, and scatters
+ * the fields into the four row families.  It READS the list, f->term and
+ * f->state; of p it reads num_groups (G), group_offset, num_slots (S) and
+ * stride and nothing else.  It writes nothing resident: only the rows of
+ * qe_inbox_out, which the caller points at the buffers it then passes to
+ * qe_follower_step, qe_snapshot_step, qe_progress_step and qe_vote_step.
+ *
+ * The list is in delivery order; a record's position i is its rank.  Mapping
+ * (sender group, `to` slot) to (receiver group, `from` slot) stays with the
+ * transport, as slot assignment stays with the host.
+ *
+ *  1. Class.  QE_IMSG_APP and _HEARTBEAT are class F (qe_follower_step),
+ *     QE_IMSG_SNAP is class S (qe_snapshot_step), QE_IMSG_APP_RESP ..
+ *     _TRANSFER_LEADER are class R (qe_progress_step), QE_IMSG_VOTE .. _HUP are
+ *     class V (qe_vote_step).  APP, SNAP and HEARTBEAT equal QE_OMSG_*: an
+ *     outbox `type` array can be fed in unchanged.
+ *  2. BAD.  A record whose group is outside [group_offset, group_offset + G),
+ *     whose type is none of QE_IMSG_*, or whose from >= num_slots (any type
+ *     but QE_IMSG_HUP) gets QE_ID_BAD.  It takes no further part and is not
+ *     deferred.
+ *  3. Wave forming.  Per group, over its remaining records in list order: the
+ *     first record opens the group's wave and fixes the wave's class.  A later
+ *     record joins the wave only if the group is still open, both it and the
+ *     opener are class R, and no record already in the wave has the same
+ *     `from`.  Otherwise the group closes: that record and every later record
+ *     of the group get QE_ID_DEFERRED.
+ *  4. HUP from the tick.  Where tick_action[g] & QE_TICK_HUP, the group's wave
+ *     is opened by a virtual QE_IMSG_HUP record that stands before position 0:
+ *     v_type[g] = QE_VMSG_HUP with from, term, index, log_term and flags 0 and
+ *     v_src[g] = QE_INBOX_SRC_TICK, and every list record of g is deferred.
+ *  5. Classes F, S, V.  The wave's one member is QE_ID_ROUTED as it is into
+ *     its family's rows at [g]: f_type = QE_LMSG_APP / _HEARTBEAT with from,
+ *     term, index, log_term, commit and, for an APP only, all msg_runs rows of
+ *     f_ent_len / f_ent_term at [j*stride+g] (zeros included); s_type =
+ *     QE_SMSG_SNAP with from, term, snap_index = index, snap_term = log_term
+ *     (the ConfState is not in a record: the host fills it for the groups
+ *     s_src names, as for qe_outbox's SNAP records); v_type = QE_VMSG_* with
+ *     from, term, index, log_term and flags (0 with in->flags NULL).
+ *  6. Class R.  Every wave member goes through Step's preamble with r.Term =
+ *     f->term[g], in this order:
+ *     a. term == 0 is a local message (raft/raft.go:850-851): it passes the
+ *        term comparison (6d);
+ *     b. term < r.Term: QE_ID_DROP_LOWER_TERM (:883-919: none of the response
+ *        types is answered);
+ *     c. term > r.Term: the lowest-position such member of the wave goes into
+ *        the vote rows as v_type = QE_VMSG_VOTE_RESP with from, term, index and
+ *        log_term 0 and flags QE_VMF_REJECT: QE_ID_STEPDOWN.  Every other such
+ *        member is QE_ID_DEFERRED (a later pass drops it as not leading, once
+ *        the term has risen);
+ *     d. otherwise, f->state[g] != QE_STATE_LEADER: QE_ID_DROP_NOT_LEADER
+ *        (stepFollower and stepCandidate have no arm for these messages);
+ *        else QE_ID_ROUTED into the peer rows at [from*stride+g]: r_type =
+ *        QE_MSG_* (type - 3), r_index = index, r_hint = hint, r_log_term =
+ *        log_term and r_ctx = ctx (0 with in->ctx NULL; not written with r_ctx
+ *        NULL).
+ *  7. Consequences.  In one pass a group receives messages for ONE entry point;
+ *     the one exception is an R wave that also yields one STEPDOWN vote row.
+ *     Because of it the host calls qe_progress_step BEFORE qe_vote_step on the
+ *     rows of one pass.  The preamble is evaluated at routing time and still
+ *     holds at step time, because no other call of the pass touches the group.
+ *  8. Rows.  f_type, s_type, v_type [G] and r_type (columns < G of each of the
+ *     S slot rows; the pad columns are not touched) are COMPLETE: 0 where
+ *     nothing was routed.  Every other row is written only where its type row
+ *     is non-zero.  f_src / s_src / v_src [G] and r_src [S][stride] (each
+ *     optional) get the list position of the routed record (v_src:
+ *     QE_INBOX_SRC_TICK for the virtual HUP): the host copies payloads,
+ *     ConfStates and heartbeat contexts by them.
+ *  9. disposition[i] = QE_ID_* of every record.  deferred[0 .. *deferred_count)
+ *     = the positions of the DEFERRED records, ascending; the next pass's list
+ *     is those records followed by what arrived since.
+ * 10. stats (optional): QE_STAT_GROUPS += groups with at least one record of
+ *     disposition ROUTED; QE_STAT_INBOX_ROUTED / _STEPDOWN / _DEFERRED /
+ *     _LOWER_TERM / _NOT_LEADER / _BAD += records by disposition, BAD also into
+ *     QE_STAT_INVARIANT_VIOLATIONS; QE_STAT_CHECKSUM += mix64(mix64(group *
+ *     0x9E3779B97F4A7C15 ^ 0xD1B54A32D192ED03 ^ disposition << 56 ^ type << 48 ^
+ *     from << 40) ^ i) per list record.
+ * Every array is a DEVICE pointer; scratch is qe_inbox_scratch_bytes(G, S,
+ * num_records) bytes of device memory, 8-B aligned: 4 * (3 + S) * G + n bytes
+ * plus qe_collect_scratch_bytes(n) (0 for a num_slots outside 1..16).  It is
+ * G-sized: see DESIGN.md.  Stream-ordered, no host synchronisation: an init
+ * pass over the groups, three passes over the records, and qe_collect's count
+ * and scan with a scatter of positions.  Positions are keys of 32-bit
+ * atomicMin, which is order-free: the outputs are bit-exact from run to run.
+ * QE_ERANGE: num_records > 0xFFFFFFF0.
+ * QE_EINVAL: a NULL p / f / in / out; f->term or f->state NULL; num_slots
+ * outside 1..16 or a nonzero reserved field of p; in->reserved nonzero;
+ * stride < num_groups; msg_runs > QE_MAX_MSG_RUNS, or > 0 with a NULL
+ * in->ent_len / in->ent_term / out->f_ent_len / out->f_ent_term; num_records
+ * > 0 with a NULL group / from / type / term / index / log_term / commit /
+ * hint (ctx, flags and tick_action may be NULL); a NULL row of qe_inbox_out
+ * other than v_flags, r_ctx, f_ent_len / f_ent_term (msg_runs 0) and the four
+ * *_src; scratch NULL (with num_groups > 0) or not 8-B aligned.  Every
+ * argument check runs before the first HIP call.  num_records == 0 is QE_OK
+ * with complete type rows (they may still hold tick HUPs) and *deferred_count
+ * = 0; num_groups == 0 is QE_OK with *deferred_count = 0 and nothing else
+ * written.
+ *
+ * With this call duties H4 and H6 of a host (tests/cluster_sim.py: Sim.deliver)
+ * and the QE_TICK_HUP half of H1 are optional. */
+#define QE_IMSG_APP 1                 /* MsgApp       (= QE_OMSG_APP)       */
+#define QE_IMSG_SNAP 2                /* MsgSnap      (= QE_OMSG_SNAP)      */
+#define QE_IMSG_HEARTBEAT 3           /* MsgHeartbeat (= QE_OMSG_HEARTBEAT) */
+#define QE_IMSG_APP_RESP 4            /* QE_MSG_* + 3 ...                   */
+#define QE_IMSG_APP_RESP_REJECT 5
+#define QE_IMSG_HEARTBEAT_RESP 6
+#define QE_IMSG_SNAP_STATUS 7
+#define QE_IMSG_SNAP_STATUS_REJECT 8
+#define QE_IMSG_UNREACHABLE 9
+#define QE_IMSG_TRANSFER_LEADER 10
+#define QE_IMSG_VOTE 11
+#define QE_IMSG_PREVOTE 12
+#define QE_IMSG_VOTE_RESP 13
+#define QE_IMSG_PREVOTE_RESP 14
+#define QE_IMSG_TIMEOUT_NOW 15
+#define QE_IMSG_HUP 16                /* local MsgHup; `from` is not checked */
+#define QE_ID_ROUTED 1            /* in this pass's rows                     */
+#define QE_ID_STEPDOWN 2          /* a higher-term response, as a vote row   */
+#define QE_ID_DEFERRED 3          /* waits for the next pass                 */
+#define QE_ID_DROP_LOWER_TERM 4
+#define QE_ID_DROP_NOT_LEADER 5
+#define QE_ID_BAD 255
+#define QE_INBOX_SRC_TICK 0xFFFFFFFFu /* v_src of the virtual HUP            */
+#define QE_STAT_INBOX_ROUTED QE_STAT_VOTE_WON        /* qe_inbox: records by disposition */
+#define QE_STAT_INBOX_STEPDOWN QE_STAT_STEPDOWNS
+#define QE_STAT_INBOX_DEFERRED QE_STAT_VOTE_PENDING
+#define QE_STAT_INBOX_LOWER_TERM QE_STAT_VOTE_LOST
+#define QE_STAT_INBOX_NOT_LEADER QE_STAT_REJECTED
+#define QE_STAT_INBOX_BAD QE_STAT_COMMIT_INF
+
+typedef struct qe_inbox_in {
+  uint64_t num_records;         /* n <= 0xFFFFFFF0 */
+  uint32_t msg_runs;            /* E, 0..QE_MAX_MSG_RUNS */
+  uint32_t reserved;            /* must be 0 */
+  const uint64_t *group;        /* [n] the RECEIVER's global group id */
+  const uint8_t  *from, *type;  /* [n] the sender's slot in the receiver's numbering, QE_IMSG_* */
+  const uint64_t *term, *index, *log_term, *commit;  /* [n]; index / log_term are also
+                                   Metadata.Index / Term of a MsgSnap */
+  const uint64_t *hint;         /* [n] m.RejectHint */
+  const uint32_t *ctx;          /* [n] or NULL: the context number of a MsgHeartbeatResp */
+  const uint8_t  *flags;        /* [n] or NULL: QE_VMF_* */
+  const uint32_t *ent_len;      /* [E][n] */
+  const uint64_t *ent_term;     /* [E][n] */
+  const uint8_t  *tick_action;  /* [G] or NULL: qe_tick's action row (QE_TICK_HUP is read) */
+} qe_inbox_in;
+
+typedef struct qe_inbox_out {
+  uint8_t  *f_type, *f_from;    /* [G] qe_leader_msgs */
+  uint64_t *f_term, *f_index, *f_log_term, *f_commit;
+  uint32_t *f_ent_len;          /* [E][stride] */
+  uint64_t *f_ent_term;         /* [E][stride] */
+  uint8_t  *s_type, *s_from;    /* [G] qe_snap_msgs */
+  uint64_t *s_term, *s_snap_index, *s_snap_term;
+  uint8_t  *v_type, *v_from;    /* [G] qe_vote_msgs */
+  uint64_t *v_term, *v_index, *v_log_term;
+  uint8_t  *v_flags;            /* [G] or NULL */
+  uint8_t  *r_type;             /* [S][stride] qe_peer_msgs */
+  uint64_t *r_index, *r_hint, *r_log_term;
+  uint32_t *r_ctx;              /* [S][stride] or NULL */
+  uint32_t *f_src, *s_src, *v_src;  /* [G], each or NULL */
+  uint32_t *r_src;              /* [S][stride] or NULL */
+  uint8_t  *disposition;        /* [n] QE_ID_* */
+  uint32_t *deferred;           /* [n] positions of the DEFERRED records, ascending */
+  uint64_t *deferred_count;     /* device */
+} qe_inbox_out;
+
+size_t qe_inbox_scratch_bytes(uint64_t num_groups, uint32_t num_slots, uint64_t num_records);
+int qe_inbox(const qe_progress *p, const qe_follower *f, const qe_inbox_in *in,
+             const qe_inbox_out *out, void *scratch, uint64_t *stats, void *stream);
 
 /* ---- statistics -------------------------------------------------------- */
 
