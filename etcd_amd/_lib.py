@@ -291,6 +291,25 @@ class QeInboxOut(C.Structure):
         "deferred_count")]
 
 
+# qe_replies
+QE_RMSG_BAD = 255
+QE_STAT_REPLY_APP_RESP, QE_STAT_REPLY_HEARTBEAT_RESP = 4, 6   # = QE_STAT_VOTE_WON / _PENDING
+QE_STAT_REPLY_VOTE_RESP, QE_STAT_REPLY_BAD = 7, 8             # = QE_STAT_GRANTED / _REJECTED
+QE_STAT_REPLY_VOTE_REQ, QE_STAT_REPLY_TIMEOUT_NOW = 11, 12    # = QE_STAT_ELECTIONS / _LEADERS
+
+
+class QeRepliesIn(C.Structure):
+    _fields_ = [(k, vp) for k in (
+        "term", "f_result", "f_from", "f_resp_index", "f_reject_hint", "f_resp_log_term", "f_ctx",
+        "s_result", "s_from", "s_resp_index", "v_result", "v_type", "v_from", "v_resp_term",
+        "v_req_log_term", "v_req_to", "timeout_now")] + [("reserved", u32 * 2)]
+
+
+class QeRepliesOut(C.Structure):
+    _fields_ = [("capacity", u64)] + [(k, vp) for k in (
+        "group", "to", "type", "term", "index", "log_term", "hint", "ctx", "flags", "count")]
+
+
 QE_BL_NONE, QE_BL_LEADER, QE_BL_NOT_MEMBER, QE_BL_RUNS_FULL = 0, 1, 2, 3
 QE_BL_BCAST = 1
 
@@ -375,6 +394,9 @@ PROTOTYPES = {
     "qe_inbox_scratch_bytes": (C.c_size_t, [u64, u32, u64]),
     "qe_inbox": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeFollower), C.POINTER(QeInboxIn),
                            C.POINTER(QeInboxOut), vp, vp, vp]),
+    "qe_replies_scratch_bytes": (C.c_size_t, [u64]),
+    "qe_replies": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeRepliesIn),
+                             C.POINTER(QeRepliesOut), vp, vp, vp]),
     "qe_gen_groups": (C.c_int, [C.POINTER(QeGroups), C.POINTER(QeGenParams), vp]),
     "qe_apply_append_resps": (C.c_int, [u64, u32, u64, vp, vp, u64, vp, vp, vp, vp, vp]),
     "qe_pack_confstate": (C.c_int, [C.POINTER(QeConfStateCSR), u32, vp, vp, vp, vp, vp, vp]),

@@ -12,6 +12,7 @@
 #include "qe_snap.hpp"
 #include "qe_outbox.hpp"
 #include "qe_inbox.hpp"
+#include "qe_replies.hpp"
 
 namespace qe {
 
@@ -1040,6 +1041,81 @@ int qe_outbox(const qe_progress *p, const qe_outbox_in *in, const qe_outbox_out 
   s = hip_status(hipGetLastError());
   if (s) return s;
   return dispatch_outbox_fill(a, out->msg_runs, st);
+}
+
+size_t qe_replies_scratch_bytes(uint64_t num_groups) {
+  return qe_collect_scratch_bytes(num_groups);  // (kObChunk: qe_outbox_scratch_bytes)
+}
+
+int qe_replies(const qe_progress *p, const qe_replies_in *in, const qe_replies_out *out,
+               void *scratch, uint64_t *stats, void *stream) {
+  const int rc = check_progress(p);
+  if (rc) return rc;
+  if (!in || !out || !out->count || !in->term) return QE_EINVAL;
+  if (in->reserved[0] || in->reserved[1] || p->reserved3) return QE_EINVAL;
+  if (p->stride < p->num_groups) return QE_EINVAL;
+  if (in->f_result &&
+      (!in->f_from || !in->f_resp_index || !in->f_reject_hint || !in->f_resp_log_term))
+    return QE_EINVAL;
+  if (in->s_result && (!in->s_from || !in->s_resp_index)) return QE_EINVAL;
+  if (in->v_result && (!in->v_type || !in->v_from || !in->v_resp_term || !in->v_req_log_term ||
+                       !in->v_req_to || !p->last_index))
+    return QE_EINVAL;
+  if (out->capacity && (!out->group || !out->to || !out->type || !out->term || !out->index ||
+                        !out->log_term || !out->hint))
+    return QE_EINVAL;
+  if (reinterpret_cast<uintptr_t>(scratch) % 8 || (p->num_groups && !scratch)) return QE_EINVAL;
+  const uint64_t nb = (p->num_groups + kObChunk - 1) / kObChunk;
+  if (nb > 0x7FFFFFFFull) return QE_ERANGE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (p->num_groups == 0 ||
+      (!in->f_result && !in->s_result && !in->v_result && !in->timeout_now))
+    return hip_status(hipMemsetAsync(out->count, 0, sizeof(uint64_t), st));
+  RPArgs a{};
+  a.G = p->num_groups;
+  a.goff = p->group_offset;
+  a.S = p->num_slots;
+  a.wide = p->num_slots > 8;
+  a.nb = nb;
+  a.term = in->term;
+  a.f_result = in->f_result;
+  a.f_from = in->f_from;
+  a.f_resp_index = in->f_resp_index;
+  a.f_reject_hint = in->f_reject_hint;
+  a.f_resp_log_term = in->f_resp_log_term;
+  a.f_ctx = in->f_ctx;
+  a.s_result = in->s_result;
+  a.s_from = in->s_from;
+  a.s_resp_index = in->s_resp_index;
+  a.v_result = in->v_result;
+  a.v_type = in->v_type;
+  a.v_from = in->v_from;
+  a.v_resp_term = in->v_resp_term;
+  a.v_req_log_term = in->v_req_log_term;
+  a.v_req_to = in->v_req_to;
+  a.last_index = p->last_index;
+  a.timeout_now = in->timeout_now;
+  a.cap = out->capacity;
+  a.o_group = out->group;
+  a.o_to = out->to;
+  a.o_type = out->type;
+  a.o_term = out->term;
+  a.o_index = out->index;
+  a.o_log_term = out->log_term;
+  a.o_hint = out->hint;
+  a.o_ctx = out->ctx;
+  a.o_flags = out->flags;
+  a.stats = stats;
+  // scratch: offsets (u64, 8-B aligned at the start), then counts (u32), as qe_collect
+  uint64_t *offsets = static_cast<uint64_t *>(scratch);
+  a.offsets = offsets;
+  a.counts = reinterpret_cast<uint32_t *>(offsets + nb);
+  int s = dispatch_replies_count(a, st);
+  if (s) return s;
+  hipLaunchKernelGGL(k_collect_scan, dim3(1), dim3(1024), 0, st, a.counts, nb, offsets, out->count);
+  s = hip_status(hipGetLastError());
+  if (s) return s;
+  return dispatch_replies_fill(a, st);
 }
 
 size_t qe_inbox_scratch_bytes(uint64_t num_groups, uint32_t num_slots, uint64_t num_records) {

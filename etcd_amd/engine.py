@@ -1168,6 +1168,74 @@ def outbox(ps, term, ob, sent=None, snap=None, index=None, next_before=None, hb_
     return ob
 
 
+class Replies(_Rows):
+    """The record arrays of qe_replies (qe_replies_out) for up to `capacity`
+    messages, in the layout an Inbox takes: group / term / index / log_term /
+    hint int64 storage of the u64 fields, to / type u8 (QE_IMSG_* or
+    QE_RMSG_BAD), ctx int32 and flags u8 (QE_VMF_*; ctx=False / flags=False
+    leave the row out: not written), and `count` (int64[1]): the records asked
+    for, which may exceed capacity.  The scratch of the call is cached here."""
+
+    FIELDS = ("group:u64 to:u8 type:u8 term:u64 index:u64 log_term:u64 hint:u64 ctx:u32? "
+              "flags:u8? count:u64")
+
+    def __init__(self, ps, capacity, ctx=True, flags=True):
+        dev, i64, u8 = ps.device, torch.int64, torch.uint8
+        self.capacity = int(capacity)
+        n = max(1, self.capacity)
+        for k in ("group", "term", "index", "log_term", "hint"):
+            setattr(self, k, torch.zeros(n, dtype=i64, device=dev))
+        self.to = torch.zeros(n, dtype=u8, device=dev)
+        self.type = torch.zeros(n, dtype=u8, device=dev)
+        self.ctx = torch.zeros(n, dtype=torch.int32, device=dev) if ctx else None
+        self.flags = torch.zeros(n, dtype=u8, device=dev) if flags else None
+        self.count = torch.zeros(1, dtype=i64, device=dev)
+        self.scratch = None
+
+    def struct(self):
+        return _lib.QeRepliesOut(self.capacity, *[_ptr(getattr(self, k)) for k in self.ARRAYS])
+
+    def records(self):
+        """-> (count, the rows cut to min(count, capacity) as numpy arrays,
+        None for a row left out)."""
+        count = int(self.count.item())
+        n = min(count, self.capacity)
+        h = self.host()
+        return count, {k: None if h[k] is None else h[k][:n] for k in self.ARRAYS if k != "count"}
+
+
+def replies(ps, term, rp, follow=None, snap=None, vote=None, timeout_now=None, f_ctx=None,
+            stats=None):
+    """qe_replies: what the receiver-side calls sent -> the messages as a dense
+    list in `rp`, in (tile, kind, slot, group) order.  follow = (LeaderMsgs,
+    FollowerOut), snap = (SnapMsgs, SnapOut) and vote = (VoteMsgs, VoteOut) are
+    the message and output objects of follower_step / snapshot_step / vote_step;
+    timeout_now is PeerMsgs.timeout_now; f_ctx [G] int32 the contexts the
+    heartbeats carried.  `term` is the Follower's term row AFTER those calls.
+    Nothing of `ps` is written."""
+    lib = _lib.lib()
+    if rp.scratch is None:
+        rp.scratch = torch.empty((lib.qe_replies_scratch_bytes(ps.G) + 7) // 8 + 1,
+                                 dtype=torch.int64, device=ps.device)
+    i = _lib.QeRepliesIn(term=_ptr(term), timeout_now=_ptr(timeout_now), f_ctx=_ptr(f_ctx))
+    if follow is not None:
+        m, o = follow
+        i.f_result, i.f_from, i.f_resp_index = _ptr(o.result), _ptr(m.from_), _ptr(o.resp_index)
+        i.f_reject_hint, i.f_resp_log_term = _ptr(o.reject_hint), _ptr(o.resp_log_term)
+    if snap is not None:
+        m, o = snap
+        i.s_result, i.s_from, i.s_resp_index = _ptr(o.result), _ptr(m.from_), _ptr(o.resp_index)
+    if vote is not None:
+        m, o = vote
+        i.v_result, i.v_type, i.v_from = _ptr(o.result), _ptr(m.type), _ptr(m.from_)
+        i.v_resp_term, i.v_req_log_term = _ptr(o.resp_term), _ptr(o.req_log_term)
+        i.v_req_to = _ptr(o.req_to)
+    p, o = ps.struct(), rp.struct()
+    check("qe_replies", lib.qe_replies(C.byref(p), C.byref(i), C.byref(o), _ptr(rp.scratch),
+                                       _ptr(stats), _stream(ps.device)))
+    return rp
+
+
 class Inbox(_Rows):
     """The record list of qe_inbox (qe_inbox_in) for up to `capacity` delivered
     messages, and the per-record outputs: group / term / index / log_term /

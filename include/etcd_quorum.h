@@ -810,6 +810,8 @@ int qe_tick(const qe_progress *p, const qe_timers *t, const qe_tick_out *out,
  * HEARTBEAT_RESP) and append_from (ci of an accept, else 0); reject_hint and
  * resp_log_term only where result == QE_FR_APP_REJECT.  The heartbeat's
  * context is not an input: the response echoes it, the host copies it.
+ * Building the MsgAppResp / MsgHeartbeatResp of a result from these rows is
+ * optional for a host now: qe_replies lists these messages on the device.
  * stats (over the groups with type != NONE): QE_STAT_GROUPS += 1;
  * QE_STAT_GRANTED += result == APP_ACCEPT; QE_STAT_REJECTED += result ==
  * APP_REJECT; QE_STAT_FOLLOW_APPENDED += lastnewi - ci + 1 where ci != 0;
@@ -956,7 +958,8 @@ int qe_follower_step(const qe_progress *p, const qe_follower *f, const qe_leader
  *     write req_log_term = lastTerm and req_to = (inc | out) & ~self: the host
  *     sends Msg{Pre}Vote{Term: resp_term, Index: last_index, LogTerm:
  *     req_log_term} to req_to and adds the transfer context to a campaign it
- *     began with TIMEOUT_NOW.
+ *     began with TIMEOUT_NOW.  Both are optional now: qe_replies lists the
+ *     requests, with QE_VMF_FORCE where the campaign began with TIMEOUT_NOW.
  *  7. Won (becomeLeader's header part): state = leader, lead = self,
  *     lead_transferee = none, voted = granted = 0, RESET, elected[g] = 1,
  *     QE_VR_WON.  The Progress reset, the empty entry and the bcast are
@@ -967,6 +970,9 @@ int qe_follower_step(const qe_progress *p, const qe_follower *f, const qe_leader
  * (elected 1 only where result == WON; events 0 where none was raised): they
  * are a complete qe_leader.elected and qe_timers.events row.  resp_term only
  * for GRANT / REJECT / CAMPAIGN_*; req_log_term and req_to only for CAMPAIGN_*.
+ * Sending the Msg{Pre}VoteResp of a GRANT / REJECT and the requests of a
+ * campaign from these rows is optional for a host now: qe_replies lists these
+ * messages on the device.
  * stats (over the groups with type != NONE): QE_STAT_GROUPS += 1;
  * QE_STAT_GRANTED += result == GRANT; QE_STAT_REJECTED += result == REJECT;
  * QE_STAT_VOTE_PENDING += result == PENDING; QE_STAT_ELECTIONS +=
@@ -1574,7 +1580,8 @@ int qe_compact(const qe_progress *p, const qe_compaction *c, uint64_t *stats, vo
  * Outputs: result[g] and events[g] (when non-NULL) for every group, events 0
  * where none was raised, so the array is a complete qe_timers.events row.
  * resp_index only where a MsgAppResp goes out: STALE, NOT_MEMBER,
- * FAST_FORWARD, RESTORED.
+ * FAST_FORWARD, RESTORED.  Sending that MsgAppResp from the rows is optional
+ * for a host now: qe_replies lists these messages on the device.
  * stats (over the groups with type != NONE): QE_STAT_GROUPS += 1;
  * QE_STAT_GRANTED += RESTORED; QE_STAT_REJECTED += STALE or NOT_MEMBER;
  * QE_STAT_COMMIT_ADVANCED += committed rose; QE_STAT_INVARIANT_VIOLATIONS +=
@@ -1821,6 +1828,10 @@ int qe_outbox(const qe_progress *p, const qe_outbox_in *in, const qe_outbox_out 
  *     Because of it the host calls qe_progress_step BEFORE qe_vote_step on the
  *     rows of one pass.  The preamble is evaluated at routing time and still
  *     holds at step time, because no other call of the pass touches the group.
+ *     The same exception is the one case where qe_replies, listing the whole
+ *     pass in one call, is inexact: the MsgTimeoutNow of such a group would
+ *     carry the term the STEPDOWN row raised (qe_replies rule 5); a host that
+ *     drives transfers lists timeout_now between the two calls.
  *  8. Rows.  f_type, s_type, v_type [G] and r_type (columns < G of each of the
  *     S slot rows; the pad columns are not touched) are COMPLETE: 0 where
  *     nothing was routed.  Every other row is written only where its type row
@@ -1929,6 +1940,143 @@ typedef struct qe_inbox_out {
 size_t qe_inbox_scratch_bytes(uint64_t num_groups, uint32_t num_slots, uint64_t num_records);
 int qe_inbox(const qe_progress *p, const qe_follower *f, const qe_inbox_in *in,
              const qe_inbox_out *out, void *scratch, uint64_t *stats, void *stream);
+
+/* qe_replies (additive in ABI 8): the messages the RECEIVER-side calls sent,
+ * as a dense, ordered list of records on the device, in the record layout
+ * qe_inbox consumes (QE_IMSG_* types) -- the half of Ready.Messages that
+ * qe_outbox does not list.  qe_follower_step, qe_snapshot_step and
+ * qe_vote_step report a send as a result code and a few rows, qe_progress_step
+ * its MsgTimeoutNow as a mask; this call turns them into MsgAppResp /
+ * MsgHeartbeatResp, Msg{Pre}VoteResp, Msg{Pre}Vote and MsgTimeoutNow records.
+ * With qe_outbox and qe_inbox the loop tick -> step -> (outbox + replies) ->
+ * transport -> inbox -> step moves no G-sized row to the host in either
+ * direction.  It writes nothing resident.  Of p it reads num_groups (G),
+ * group_offset, num_slots (S), stride and, when the V family is given,
+ * last_index, and nothing else.  A family is present iff its result row is
+ * non-NULL; full = (1 << S) - 1.
+ *
+ *  1. Kinds, in this order per group:
+ *     F response, f_result[g] one of
+ *       QE_FR_LOWER_TERM_RESP: QE_IMSG_APP_RESP with index 0 (the empty
+ *         MsgAppResp of raft/raft.go:906);
+ *       QE_FR_HEARTBEAT_RESP: QE_IMSG_HEARTBEAT_RESP with ctx = f_ctx[g], 0 with
+ *         f_ctx NULL (handleHeartbeat echoes m.Context, :1515);
+ *       QE_FR_APP_ACCEPT / QE_FR_APP_STALE: QE_IMSG_APP_RESP with index =
+ *         f_resp_index[g] (:1482, :1477);
+ *       QE_FR_APP_REJECT: QE_IMSG_APP_RESP_REJECT with index = f_resp_index[g],
+ *         hint = f_reject_hint[g], log_term = f_resp_log_term[g] (:1502-1509);
+ *       each with to = f_from[g] and term = in->term[g].
+ *     S response, s_result[g] one of QE_SR_STALE, QE_SR_NOT_MEMBER,
+ *       QE_SR_FAST_FORWARD, QE_SR_RESTORED: QE_IMSG_APP_RESP with index =
+ *       s_resp_index[g], to = s_from[g], term = in->term[g] (:1523, :1527).
+ *     V response, v_result[g] QE_VR_GRANT or QE_VR_REJECT: QE_IMSG_VOTE_RESP
+ *       for v_type[g] == QE_VMSG_VOTE, QE_IMSG_PREVOTE_RESP for QE_VMSG_PREVOTE
+ *       (voteRespMsgType), QE_RMSG_BAD for any other v_type; to = v_from[g],
+ *       term = v_resp_term[g], flags = QE_VMF_REJECT for a REJECT (:968, :977,
+ *       :913).
+ *     V request, v_result[g] QE_VR_CAMPAIGN_VOTE or QE_VR_CAMPAIGN_PREVOTE: one
+ *       QE_IMSG_VOTE / QE_IMSG_PREVOTE to every set bit of v_req_to[g] & full,
+ *       with term = v_resp_term[g], index = p->last_index[g], log_term =
+ *       v_req_log_term[g] (:833), and flags = QE_VMF_FORCE where v_type[g] ==
+ *       QE_VMSG_TIMEOUT_NOW and the result is CAMPAIGN_VOTE: the
+ *       campaignTransfer context (:818-835).
+ *     T, one QE_IMSG_TIMEOUT_NOW to every set bit of timeout_now[g] & full,
+ *       with term = in->term[g] (sendTimeoutNow, :1722-1724).
+ *     Every other result code, every refused result (>= 16) and every absent
+ *     family yields nothing.  A field a kind does not name is 0.  group =
+ *     group_offset + g: the SENDER.
+ *  2. BAD.  A single-`to` record (F, S, V response) whose to >= num_slots gets
+ *     type QE_RMSG_BAD, as does the V response whose v_type is no request.  It
+ *     keeps group, to and term as computed; every other field is 0.  *count
+ *     depends on the result rows and the masks alone, never on a from / type row.
+ *  3. Order.  Records are listed by ascending tile (g / 64), then kind (F, S, V
+ *     response, V request, T); within the three single-record kinds then g,
+ *     within the two mask kinds then slot, then g: qe_outbox's order with the
+ *     kind in front of the slot.  The order is part of the contract.
+ *  4. Truncation, as qe_outbox: a record at a position >= capacity is not
+ *     written; *count is still the full number, and nothing at or past
+ *     min(*count, capacity) is touched in any output array.
+ *  5. The term row.  in->term is qe_follower.term as it stands when qe_replies
+ *     runs: a call lists the outputs of the step calls made since that row
+ *     last changed for the groups concerned (F, S and T records carry the
+ *     receiver's term after its step; V records carry v_resp_term).  Listing a
+ *     whole qe_inbox pass in one call is inexact in ONE case (qe_inbox rule 7):
+ *     a group whose R wave set a timeout_now bit in qe_progress_step and whose
+ *     STEPDOWN vote row then raised the term in qe_vote_step of the same pass.
+ *     Its MsgTimeoutNow would carry the new term, where r.send (:415) stamps
+ *     the term of the leader that sent it.  A host that drives leadership
+ *     transfers lists timeout_now in a call of its own, between
+ *     qe_progress_step and qe_vote_step.
+ *  6. stats (optional), over every record asked for, those past capacity too:
+ *     QE_STAT_GROUPS += groups with at least one record;
+ *     QE_STAT_REPLY_APP_RESP / _HEARTBEAT_RESP / _VOTE_RESP / _VOTE_REQ /
+ *     _TIMEOUT_NOW / _BAD += records by type (APP_RESP: accept, stale, lower
+ *     term, snapshot and reject records; a BAD record counts as BAD alone), BAD
+ *     also into QE_STAT_INVARIANT_VIOLATIONS; QE_STAT_CHECKSUM += h6 per record,
+ *     h1 = mix64(group * 0x9E3779B97F4A7C15 ^ 0xA0761D6478BD642F ^ type << 56 ^
+ *     to << 48), h2 = mix64(h1 ^ term), h3 = mix64(h2 ^ index), h4 = mix64(h3 ^
+ *     log_term), h5 = mix64(h4 ^ hint), h6 = mix64(h5 ^ (ctx | (uint64)flags <<
+ *     32)), the fields as the record holds them (ctx and flags too where their
+ *     arrays are NULL).
+ * `count` and every array of both structs are DEVICE pointers; scratch is
+ * qe_replies_scratch_bytes(num_groups) (== qe_collect_scratch_bytes) bytes of
+ * device memory, 8-B aligned.  Stream-ordered: three kernels (count per
+ * 4096-group chunk, the scan of qe_collect, fill), no host synchronisation.
+ * QE_EINVAL: a NULL p / in / out / count / term; scratch NULL (with num_groups
+ * > 0) or not 8-B aligned; num_slots outside 1..16; a nonzero reserved field
+ * of p or in; stride < num_groups; f_result without f_from, f_resp_index,
+ * f_reject_hint or f_resp_log_term; s_result without s_from or s_resp_index;
+ * v_result without v_type, v_from, v_resp_term, v_req_log_term, v_req_to or
+ * p->last_index; capacity > 0 with a NULL group / to / type / term / index /
+ * log_term / hint array (ctx and flags may be NULL: not written).  Every
+ * argument check runs before the first HIP call.  num_groups == 0 is QE_OK
+ * with *count = 0, and so is a call with every family absent.
+ *
+ * With this call duty H8 of a host (tests/cluster_sim.py), the vote half of H4
+ * and the MsgTimeoutNow of a transfer are optional: the host copies
+ * min(*count, capacity) records instead of the G-sized result rows it would
+ * walk.  MsgSnapStatus (H11) stays the transport's. */
+#define QE_RMSG_BAD 255      /* a response whose `to` is no slot, or a GRANT / REJECT
+                                whose message type is no request */
+#define QE_STAT_REPLY_APP_RESP QE_STAT_VOTE_WON            /* qe_replies: records by type */
+#define QE_STAT_REPLY_HEARTBEAT_RESP QE_STAT_VOTE_PENDING
+#define QE_STAT_REPLY_VOTE_RESP QE_STAT_GRANTED
+#define QE_STAT_REPLY_VOTE_REQ QE_STAT_ELECTIONS
+#define QE_STAT_REPLY_TIMEOUT_NOW QE_STAT_LEADERS
+#define QE_STAT_REPLY_BAD QE_STAT_REJECTED
+
+typedef struct qe_replies_in {
+  const uint64_t *term;          /* [G] required: qe_follower.term as it stands AFTER the listed calls */
+  /* F: qe_follower_step (family present iff f_result != NULL) */
+  const uint8_t  *f_result;      /* [G] qe_follower_out.result */
+  const uint8_t  *f_from;        /* [G] qe_leader_msgs.from */
+  const uint64_t *f_resp_index, *f_reject_hint, *f_resp_log_term;   /* [G] */
+  const uint32_t *f_ctx;         /* [G] or NULL: the context the heartbeat carried (echoed) */
+  /* S: qe_snapshot_step (present iff s_result != NULL) */
+  const uint8_t  *s_result, *s_from;   /* [G] */
+  const uint64_t *s_resp_index;        /* [G] */
+  /* V: qe_vote_step (present iff v_result != NULL) */
+  const uint8_t  *v_result, *v_type, *v_from;   /* [G] qe_vote_out.result, qe_vote_msgs.type / from */
+  const uint64_t *v_resp_term, *v_req_log_term; /* [G] */
+  const void     *v_req_to;      /* [G] mask-typed */
+  /* T: qe_progress_step */
+  const void     *timeout_now;   /* [G] mask-typed or NULL */
+  uint32_t reserved[2];          /* must be 0 */
+} qe_replies_in;
+
+typedef struct qe_replies_out {
+  uint64_t capacity;
+  uint64_t *group;               /* [capacity] group_offset + g (the SENDER) */
+  uint8_t  *to, *type;           /* [capacity] slot, QE_IMSG_* or QE_RMSG_BAD */
+  uint64_t *term, *index, *log_term, *hint;   /* [capacity] */
+  uint32_t *ctx;                 /* [capacity] or NULL */
+  uint8_t  *flags;               /* [capacity] or NULL: QE_VMF_* */
+  uint64_t *count;               /* device: records asked for (may exceed capacity) */
+} qe_replies_out;
+
+size_t qe_replies_scratch_bytes(uint64_t num_groups);   /* == qe_collect_scratch_bytes */
+int qe_replies(const qe_progress *p, const qe_replies_in *in, const qe_replies_out *out,
+               void *scratch, uint64_t *stats, void *stream);
 
 /* ---- statistics -------------------------------------------------------- */
 
