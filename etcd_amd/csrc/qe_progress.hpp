@@ -2141,14 +2141,32 @@ __global__ __launch_bounds__(kBlock) void k_become_leader(PArgs a) {
     const uint64_t c0 = bld64(r_c, o8);
     const uint32_t rc = (a.R && a.run_count) ? bld8(mk_rsrc(a.run_count + g0, n), o1) : 0u;
     const bool member = self < static_cast<uint32_t>(S) && ((trk >> self) & 1u) != 0;
-    // (a full run table refuses only when a new run is needed; checked
-    // against the last run's term below, conservatively here)
-    const uint32_t res = !el ? QE_BL_NONE
-                             : (!member ? QE_BL_NOT_MEMBER
-                                        : ((a.R && rc >= a.R) ? QE_BL_RUNS_FULL : QE_BL_LEADER));
+    // the log's last run, for the elected members: a run of the new term (a
+    // bootstrap snapshot of the new leader's own term) is entered, not
+    // appended to, so a full run table refuses only a lower last term
+    const bool cand = el && member;
+    const uint64_t term = bld64(mk_rsrc(a.bl_term + g0, n * 8), cand ? o8 : kOOB);
+    bool same = false;
+    uint64_t ts_same = 0;
+    if (a.R && __builtin_amdgcn_ballot_w64(cand)) {
+      for (uint32_t r = 0; r < a.R; r++) {  // the last run, a row per lane
+        const bool on = cand && rc == r + 1;
+        if (!__builtin_amdgcn_ballot_w64(on)) continue;
+        const uint64_t row = static_cast<uint64_t>(r) * a.stride + g0;
+        const uint64_t f = bld64(mk_rsrc(a.run_first + row, n * 8), on ? o8 : kOOB);
+        const uint64_t tt = bld64(mk_rsrc(a.run_term + row, n * 8), on ? o8 : kOOB);
+        if (on && tt == term) {
+          same = true;
+          ts_same = f;
+        }
+      }
+    }
+    const uint32_t res =
+        !el ? QE_BL_NONE
+            : (!member ? QE_BL_NOT_MEMBER
+                       : ((a.R && rc >= a.R && !same) ? QE_BL_RUNS_FULL : QE_BL_LEADER));
     const bool go = res == QE_BL_LEADER;
     const uint32_t k8 = go ? o8 : kOOB;
-    const uint64_t term = bld64(mk_rsrc(a.bl_term + g0, n * 8), k8);
     const uint64_t fi = bld64(mk_rsrc(a.first_index + g0, n * 8), k8);
     const uint64_t sn = a.snap_index ? bld64(mk_rsrc(a.snap_index + g0, n * 8), k8) : fi - 1;
     uint64_t c = c0;
@@ -2158,20 +2176,8 @@ __global__ __launch_bounds__(kBlock) void k_become_leader(PArgs a) {
       // the log model enters the term: a run of `term` from lastIndex + 1 --
       // unless the log's last run has that term already (a bootstrap
       // snapshot of the new leader's own term): the term then starts there
-      uint64_t ts2 = li2;
+      const uint64_t ts2 = same ? ts_same : li2;
       if (a.R) {
-        bool same = false;
-        for (uint32_t r = 0; r < a.R; r++) {  // the last run, a row per lane
-          const bool on = go && rc == r + 1;
-          if (!__builtin_amdgcn_ballot_w64(on)) continue;
-          const uint64_t row = static_cast<uint64_t>(r) * a.stride + g0;
-          const uint64_t f = bld64(mk_rsrc(a.run_first + row, n * 8), on ? o8 : kOOB);
-          const uint64_t tt = bld64(mk_rsrc(a.run_term + row, n * 8), on ? o8 : kOOB);
-          if (on && tt == term) {
-            same = true;
-            ts2 = f;
-          }
-        }
         for (uint32_t r = 0; r < a.R; r++) {
           const bool on = go && !same && rc == r;
           if (!__builtin_amdgcn_ballot_w64(on)) continue;

@@ -1153,9 +1153,13 @@ int qe_propose(const qe_progress *p, const qe_proposals *prop, uint64_t *stats, 
 #define QE_BL_NOT_MEMBER 2  /* self_slot holds no Progress: the reference would
                                panic (a candidate is promotable, so a voter);
                                nothing changes                               */
-#define QE_BL_RUNS_FULL 3   /* the new term's run does not fit the log model's
-                               log_runs: nothing changes (qe_compact frees
-                               rows on the device, then retry)               */
+#define QE_BL_RUNS_FULL 3   /* a run of the new term would have to be appended
+                               and run_count == log_runs: nothing changes
+                               (qe_compact frees rows on the device, then
+                               retry).  A full table whose last run already
+                               has term[g] (a bootstrap snapshot of the new
+                               leader's own term) appends nothing and is no
+                               refusal: QE_BL_LEADER                         */
 #define QE_BL_BCAST 1u      /* qe_leader.flags: then bcastAppend, as
                                stepCandidate does after winning (raft.go:
                                1405-1407)                                     */
@@ -1185,7 +1189,9 @@ typedef struct qe_leader {
  *     requests' context numbers, so a late response for one finds nothing);
  *   pendingConfIndex = lastIndex; uncommittedSize = 0;
  *   the log model enters the term: a run [lastIndex + 1, ...) of term[g] is
- *     appended to the run table and term_start = lastIndex + 1;
+ *     appended to the run table and term_start = lastIndex + 1 -- unless the
+ *     last run has term[g] already: run_count stays and term_start = that
+ *     run's first index;
  *   appendEntry of the empty entry (:621-642): lastIndex + 1, the leader's
  *     MaybeUpdate, maybeCommit (a one-voter config commits it at once);
  *   QE_BL_BCAST: bcastAppend (every tracked slot but the leader's, the

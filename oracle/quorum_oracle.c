@@ -1824,7 +1824,8 @@ void orc_propose_batch(const orc_prog *a, const orc_props *q, uint64_t *stats) {
  * the empty entry (lastIndex + 1, the leader's MaybeUpdate, maybeCommit) and,
  * with flags & 1, stepCandidate's bcastAppend (:1405-1407).  result: 0 not
  * elected, 1 leader, 2 no Progress for the leader (the reference panics), 3
- * the run table is full (nothing changes). */
+ * the run table is full and the last run's term is not term[g], so a run
+ * would have to be appended (nothing changes). */
 uint64_t orc_checksum_leader(uint64_t gid, uint32_t result, uint64_t committed, uint32_t sent,
                              uint32_t snap) {
   uint64_t h = gid * PHI;
@@ -1852,7 +1853,9 @@ void orc_become_leader_batch(const orc_prog *a, const uint8_t *elected, const ui
       uint32_t mo = a->out ? ld_mask(a->out, mb, g) & full : 0;
       uint32_t rc = (a->R && run_count) ? run_count[g] : 0;
       if (!(self < S && ((trk >> self) & 1u))) res = 2;
-      else if (a->R && rc >= a->R) res = 3;
+      else if (a->R && rc >= a->R &&
+               !(rc > 0 && rc <= a->R && run_term[(rc - 1) * a->stride + g] == term[g]))
+        res = 3; /* full, and the last run's term is not the new one */
       else {
         res = 1;
         uint64_t li = last_index[g];

@@ -228,8 +228,10 @@ class ModelBackend:
     """One method per entry point, on the models alone.  Each returns the
     model's outputs; the state is `self.w`."""
 
+    WORLD = World  # a subclass may compose another initial state (tests/trace_cluster.py)
+
     def __init__(self, p, vote_step=vm.step, follower_step=fm.step):
-        self.p, self.w = p, World(p)
+        self.p, self.w = p, self.WORLD(p)
         self.vote_step_fn, self.follower_step_fn = vote_step, follower_step
         self.calls = Counter()
 

@@ -130,8 +130,10 @@ def test_switch_config_argument_errors(eng):
 def test_become_leader_matches_oracle(eng, S, F, masks, max_ents, reads, ring16):
     """qe_become_leader (raft.becomeLeader + reset, raft.go:724-759,
     :590-613) against the oracle on random states: elected and not, leaders
-    without a Progress, full run tables, a new term equal to the last run's
-    (the bootstrap case), ReadIndex queues dropped, bcastAppend's probes
+    without a Progress, full run tables (refused only where a run would have
+    to be appended: a full table whose last run has the new term leads), a new
+    term equal to the last run's (the bootstrap case), ReadIndex queues
+    dropped, bcastAppend's probes
     (compacted logs: nothing to an inactive peer); every Progress field, the
     log model (runs, term start, lastIndex, committed), the outputs and the
     statistics equal the oracle's."""
@@ -170,5 +172,75 @@ def test_become_leader_matches_oracle(eng, S, F, masks, max_ents, reads, ring16)
         got = eng.stats_reduce(st).cpu().numpy().view(np.uint64)
         np.testing.assert_array_equal(got, o.stats, err_msg="stats")
         assert {0, 1, 2, 3} <= set(np.unique(o.result).tolist()) or S == 1
+        if bcast:  # (the first election: the second's terms are all new)
+            full_same = (el != 0) & (o.result == 1) & (pb.run_count == R) & (term == last_term)
+            assert full_same.any(), "no full table with the new term in this state"
         assert not bcast or S == 1 or o.sent.any()
         term = term + np.uint64(1)  # a second election on the new state
+
+
+def full_table_state(G, S, R, F=4):
+    """Every group a candidate on a FULL run table (run_count == R): even
+    groups' last run has term 5, odd groups' term 4; terms ascend along the
+    table, lastIndex 2 * R + 3.  -> (ProgressBatch, the last run's first
+    index)."""
+    md = orc.mask_dtype(S)
+    pb = orc.ProgressBatch(G, S, F, R, stride=G + 3, max_ents=0)
+    pb.inc = np.full(G, (1 << S) - 1, md)
+    pb.tracked = np.full(G, (1 << S) - 1, md)
+    pb.self_slot = (np.arange(G) % S).astype(np.uint8)
+    pb.lead_transferee = np.full(G, 0xFF, np.uint8)
+    pb.snap_index = np.full(G, 2, np.uint64)
+    g = np.arange(G)
+    for r in range(R):
+        pb.run_first[r * pb.stride + g] = 2 + 2 * r
+        pb.run_term[r * pb.stride + g] = (5 - (g & 1)) if r == R - 1 else r + 1
+    pb.run_count[:] = R
+    pb.first_index[:] = 3
+    pb.last_index[:] = 2 * R + 3
+    pb.committed[:] = 2 * R + 1
+    pb.next[:] = 1
+    return pb, 2 + 2 * (R - 1)
+
+
+@pytest.mark.parametrize("R", [1, 3])
+def test_become_leader_full_run_table(eng, R):
+    """A full run table (run_count == log_runs) refuses becomeLeader only
+    where a run would have to be appended.  G = 65 (one full tile and one
+    lane), the two kinds mixed across lanes: even groups' last run already has
+    the new term 5 -> QE_BL_LEADER, run_count unchanged, term_start = that
+    run's first index; odd groups' last run has term 4 -> QE_BL_RUNS_FULL and
+    nothing changes.  R = 1 is campaign.txt's table (every node on a
+    snapshot of the term the first leader wins).  Everything against the
+    oracle; the expected results are stated here, not taken from it."""
+    G, S = 65, 3
+    pb, last_first = full_table_state(G, S, R)
+    if R == 1:  # one run: the snapshot's; odd groups' snapshot term is lower
+        assert set(pb.run_term[:G].tolist()) == {4, 5}
+    before = pb.copy()
+    ps = to_device(eng, pb, ("inc",), EXTRAS)
+    term = np.full(G, 5, np.uint64)
+    ld = eng.Leader(ps, None, bcast=True)
+    ld.term.copy_(torch.from_numpy(term.view(np.int64)).to(DEV))
+    st = eng.stats_buffer(DEV)
+    eng.become_leader(ps, ld, stats=st)
+    o = orc.become_leader(pb, term, bcast=True)
+    even = np.arange(G) % 2 == 0
+    want = np.where(even, 1, 3).astype(np.uint8)  # QE_BL_LEADER / QE_BL_RUNS_FULL
+    np.testing.assert_array_equal(o.result, want, err_msg="oracle result")
+    np.testing.assert_array_equal(ld.result.cpu().numpy(), want, err_msg="result")
+    md = orc.mask_dtype(S)
+    np.testing.assert_array_equal(ld.sent.cpu().numpy().view(md), o.sent, err_msg="sent")
+    np.testing.assert_array_equal(ld.snap.cpu().numpy().view(md), o.snap, err_msg="snap")
+    h = ps.host()
+    for k in ("term_start", "last_index", "run_count", "run_first", "run_term", "committed"):
+        np.testing.assert_array_equal(h[k], getattr(pb, k), err_msg=k)
+    assert (h["run_count"] == R).all()
+    assert (h["term_start"][even] == last_first).all()
+    assert (h["last_index"][even] == before.last_index[even] + 1).all()
+    for k in ("term_start", "last_index", "committed"):  # refused: nothing changes
+        np.testing.assert_array_equal(h[k][~even], getattr(before, k)[~even], err_msg=k)
+    assert (o.sent[even] != 0).all() and not o.sent[~even].any()
+    assert_same(ps, pb)
+    got = eng.stats_reduce(st).cpu().numpy().view(np.uint64)
+    np.testing.assert_array_equal(got, o.stats, err_msg="stats")

@@ -433,6 +433,35 @@ def probe_and_replicate(leader_factory, elector):
     return checked
 
 
+# The leaders that already lead where the replayed part of their trace begins
+# (the docstrings of the replay functions below say where each value comes
+# from; pci of the snapshot trace: becomeLeader at lastIndex 10, the snapshot
+# `add-nodes ... index=10` starts from); tests/trace_cluster.py starts its
+# node 1 from the same values.
+LEADER_START = {
+    "snapshot_succeed_via_app_resp.txt": dict(
+        start="status 1", last_index=11, committed=11, runs=[[11, 1]], first_index=12,
+        snap_index=11, term_start=11, term=1, pci=10, applied=11),
+    "confchange_v1_remove_leader.txt": dict(
+        start="log-level debug", last_index=3, committed=3, runs=[[2, 1]], first_index=3,
+        snap_index=2, term_start=2, term=1, pci=2, applied=3,
+        peers=[{"match": 3, "next": 4, "pending": 0, "state": 1, "probe_sent": False,
+                "recent_active": True, "ring": []} for _ in range(3)]),
+}
+# the two add_single traces (the docstring of _confchange_add_single): the state
+# after the first Ready of `stabilize` applied the conf change at 4; that Ready
+# (the command's first block) lies before it, switchToConfig right after it
+for _name in ("confchange_v1_add_single.txt", "confchange_v2_add_single_auto.txt"):
+    LEADER_START[_name] = dict(
+        start="stabilize", skip_blocks=1, switch_first=True, voters=(1, 2),
+        last_index=4, committed=4, runs=[[2, 1]], first_index=3, snap_index=4, term_start=2,
+        term=1, pci=4, applied=4,
+        peers=[{"match": 4, "next": 5, "pending": 0, "state": 1, "probe_sent": False,
+                "recent_active": True, "ring": []},
+               {"match": 0, "next": 4, "pending": 0, "state": 0, "probe_sent": False,
+                "recent_active": True, "ring": []}])
+
+
 def snapshot_succeed_via_app_resp(leader_factory, elector):
     """raft/testdata/snapshot_succeed_via_app_resp.txt from its first
     `status 1`: the state is the one that status prints (3 voters, node 3
@@ -440,10 +469,12 @@ def snapshot_succeed_via_app_resp(leader_factory, elector):
     (term 1) plus its empty entry 11 (term 1), compacted through 11
     (`compact 1 11`: firstIndex 12, snapshot index 11), committed 11."""
     cmds = traces()["snapshot_succeed_via_app_resp.txt"]["commands"]
-    st = command(cmds, "status 1")
+    ls = LEADER_START["snapshot_succeed_via_app_resp.txt"]
+    st = command(cmds, ls["start"])
     L = leader_factory(1, 3)
     peers = [parse_progress(st["blocks"][0]["progress"][str(k)]) for k in (1, 2, 3)]
-    L.load(11, 11, [[11, 1]], 12, peers, snap_index=11, term_start=11)
+    L.load(ls["last_index"], ls["committed"], ls["runs"], ls["first_index"], peers,
+           snap_index=ls["snap_index"], term_start=ls["term_start"])
     return L.replay(cmds, st["line"])
 
 
@@ -502,11 +533,9 @@ def _confchange_add_single(name):
         cmds = traces()[name]["commands"]
         st = command(cmds, "stabilize")
         L = leader_factory(1, 2)
-        peers = [{"match": 4, "next": 5, "pending": 0, "state": 1, "probe_sent": False,
-                  "recent_active": True, "ring": []},
-                 {"match": 0, "next": 4, "pending": 0, "state": 0, "probe_sent": False,
-                  "recent_active": True, "ring": []}]
-        L.load(4, 4, [[2, 1]], 3, peers, snap_index=4)
+        ls = LEADER_START[name]
+        L.load(ls["last_index"], ls["committed"], ls["runs"], ls["first_index"],
+               [dict(p) for p in ls["peers"]], snap_index=ls["snap_index"])
         switched = []
 
         def after(block):
@@ -575,12 +604,12 @@ def confchange_v1_remove_leader(leader_factory, elector):
     its proposals are dropped (no Progress of its own, raft.go:1023-1028),
     and it still heartbeats both followers."""
     cmds = traces()["confchange_v1_remove_leader.txt"]["commands"]
-    st = command(cmds, "log-level debug")
+    ls = LEADER_START["confchange_v1_remove_leader.txt"]
+    st = command(cmds, ls["start"])
     L = leader_factory(1, 3)
-    rep = {"match": 3, "next": 4, "pending": 0, "state": 1, "probe_sent": False,
-           "recent_active": True, "ring": []}
-    L.load(3, 3, [[2, 1]], 3, [dict(rep) for _ in range(3)], tracked=0b111, inc=0b111)
-    L.be.pci, L.be.applied = 2, 3
+    L.load(ls["last_index"], ls["committed"], ls["runs"], ls["first_index"],
+           [dict(p) for p in ls["peers"]], tracked=0b111, inc=0b111)
+    L.be.pci, L.be.applied = ls["pci"], ls["applied"]
     seen = []
 
     def after(block):
