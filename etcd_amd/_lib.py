@@ -310,6 +310,44 @@ class QeRepliesOut(C.Structure):
         "group", "to", "type", "term", "index", "log_term", "hint", "ctx", "flags", "count")]
 
 
+# qe_ready_note / qe_ready / qe_advance
+QE_RD_SOFT, QE_RD_HARD, QE_RD_MUST_SYNC, QE_RD_SNAP, QE_RD_ENTS_CUT, QE_RD_APPLY_CUT = (
+    1, 2, 4, 8, 16, 32)
+QE_ADV_OK, QE_ADV_OK_STALE_ENTRIES = 1, 2
+QE_ADV_REFUSED = 8  # outcomes >= this: nothing of the group changed
+QE_ADV_BAD_GROUP, QE_ADV_APPLIED_RANGE = 8, 9
+QE_ADV_OUTCOME, QE_ADV_AUTO_LEAVE = 0x0F, 0x10
+QE_STAT_READY_ENTRIES = 2     # = QE_STAT_COMMIT_SUM
+QE_STAT_READY_MUST_SYNC = 4   # = QE_STAT_VOTE_WON
+QE_STAT_READY_APPLY = 9       # = QE_STAT_COMMIT_ADVANCED
+
+
+class QeReadyState(C.Structure):
+    _fields_ = [(k, vp) for k in (
+        "stable", "applied", "snap_pending", "prev_term", "prev_commit", "prev_vote", "prev_lead",
+        "prev_state")]
+
+
+class QeReadyNoteIn(C.Structure):
+    _fields_ = [(k, vp) for k in ("follow_result", "append_from", "snap_result",
+                                  "snap_resp_index")]
+
+
+class QeReadyIn(C.Structure):
+    _fields_ = [("pending", vp), ("max_apply", u32), ("reserved", u32)]
+
+
+class QeReadyOut(C.Structure):
+    _fields_ = [("capacity", u64), ("ent_runs", u32), ("reserved", u32)] + [(k, vp) for k in (
+        "group", "term", "commit", "vote", "lead", "state", "flags", "ent_first", "ent_count",
+        "ent_last_term", "apply_first", "apply_count", "snap_index", "ent_len", "ent_term",
+        "apply_len", "apply_term", "count")]
+
+
+class QeAdvanceOpt(C.Structure):
+    _fields_ = [("auto_leave", vp), ("pending_conf_index", vp), ("reserved", u32 * 2)]
+
+
 QE_BL_NONE, QE_BL_LEADER, QE_BL_NOT_MEMBER, QE_BL_RUNS_FULL = 0, 1, 2, 3
 QE_BL_BCAST = 1
 
@@ -397,6 +435,14 @@ PROTOTYPES = {
     "qe_replies_scratch_bytes": (C.c_size_t, [u64]),
     "qe_replies": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeRepliesIn),
                              C.POINTER(QeRepliesOut), vp, vp, vp]),
+    "qe_ready_note": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeReadyState),
+                                C.POINTER(QeReadyNoteIn), vp]),
+    "qe_ready_scratch_bytes": (C.c_size_t, [u64]),
+    "qe_ready": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeFollower), C.POINTER(QeReadyState),
+                           C.POINTER(QeReadyIn), C.POINTER(QeReadyOut), vp, vp, vp]),
+    "qe_advance": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeFollower),
+                             C.POINTER(QeReadyState), C.POINTER(QeReadyOut),
+                             C.POINTER(QeAdvanceOpt), vp, vp]),
     "qe_gen_groups": (C.c_int, [C.POINTER(QeGroups), C.POINTER(QeGenParams), vp]),
     "qe_apply_append_resps": (C.c_int, [u64, u32, u64, vp, vp, u64, vp, vp, vp, vp, vp]),
     "qe_pack_confstate": (C.c_int, [C.POINTER(QeConfStateCSR), u32, vp, vp, vp, vp, vp, vp]),

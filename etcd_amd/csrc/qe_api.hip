@@ -13,6 +13,7 @@
 #include "qe_outbox.hpp"
 #include "qe_inbox.hpp"
 #include "qe_replies.hpp"
+#include "qe_ready.hpp"
 
 namespace qe {
 
@@ -1116,6 +1117,178 @@ int qe_replies(const qe_progress *p, const qe_replies_in *in, const qe_replies_o
   s = hip_status(hipGetLastError());
   if (s) return s;
   return dispatch_replies_fill(a, st);
+}
+
+static bool missing_ready_state(const qe_ready_state *rs) {
+  return !rs->stable || !rs->applied || !rs->snap_pending || !rs->prev_term || !rs->prev_commit ||
+         !rs->prev_vote || !rs->prev_lead || !rs->prev_state;
+}
+// the field arrays of a record list (the run arrays go with ent_runs)
+static bool missing_ready_fields(const qe_ready_out *o) {
+  return !o->group || !o->term || !o->commit || !o->vote || !o->lead || !o->state || !o->flags ||
+         !o->ent_first || !o->ent_count || !o->ent_last_term || !o->apply_first ||
+         !o->apply_count || !o->snap_index;
+}
+
+int qe_ready_note(const qe_progress *p, const qe_ready_state *rs, const qe_ready_note_in *in,
+                  void *stream) {
+  if (!p || !rs || !in || !rs->stable) return QE_EINVAL;
+  if (!in->follow_result != !in->append_from) return QE_EINVAL;
+  if (!in->snap_result != !in->snap_resp_index) return QE_EINVAL;
+  if (in->snap_result && !rs->snap_pending) return QE_EINVAL;
+  if (p->num_groups == 0 || (!in->follow_result && !in->snap_result)) return QE_OK;
+  RNArgs a{};
+  a.G = p->num_groups;
+  a.follow_result = in->follow_result;
+  a.append_from = in->append_from;
+  a.snap_result = in->snap_result;
+  a.resp_index = in->snap_resp_index;
+  a.stable = rs->stable;
+  a.snap_pending = rs->snap_pending;
+  return dispatch_ready_note(a, static_cast<hipStream_t>(stream));
+}
+
+// qe_collect's part (offsets u64, counts u32), then one flag byte per group
+// from a 16-B boundary on.
+static size_t ready_flag_offset(uint64_t num_groups) {
+  return (qe_collect_scratch_bytes(num_groups) + 15) & ~static_cast<size_t>(15);
+}
+
+size_t qe_ready_scratch_bytes(uint64_t num_groups) {
+  static_assert(kObChunk == kCollectChunk, "k_collect_scan's chunks");
+  return ready_flag_offset(num_groups) + static_cast<size_t>(num_groups) + 16;
+}
+
+int qe_ready(const qe_progress *p, const qe_follower *f, const qe_ready_state *rs,
+             const qe_ready_in *in, const qe_ready_out *out, void *scratch, uint64_t *stats,
+             void *stream) {
+  const int rc = check_progress(p);
+  if (rc) return rc;
+  if (!f || !rs || !in || !out || !out->count) return QE_EINVAL;
+  if (in->reserved || out->reserved || p->reserved3) return QE_EINVAL;
+  if (missing_log_model(p) || missing_follower(f) || missing_ready_state(rs)) return QE_EINVAL;
+  if (out->ent_runs > QE_MAX_MSG_RUNS ||
+      (out->ent_runs && (!out->ent_len || !out->ent_term || !out->apply_len || !out->apply_term)))
+    return QE_EINVAL;
+  if (out->capacity && missing_ready_fields(out)) return QE_EINVAL;
+  if (reinterpret_cast<uintptr_t>(scratch) % 8 || (p->num_groups && !scratch)) return QE_EINVAL;
+  const uint64_t nb = (p->num_groups + kObChunk - 1) / kObChunk;
+  if (nb > 0x7FFFFFFFull) return QE_ERANGE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (p->num_groups == 0) return hip_status(hipMemsetAsync(out->count, 0, sizeof(uint64_t), st));
+  RDArgs a{};
+  step_head(p, stats, a);
+  a.S = p->num_slots;
+  a.max_apply = in->max_apply;
+  a.nb = nb;
+  a.committed = p->committed;
+  a.last_index = p->last_index;
+  a.run_first = p->run_first;
+  a.run_term = p->run_term;
+  a.run_count = p->run_count;
+  a.term = f->term;
+  a.state = f->state;
+  a.lead = f->lead;
+  a.vote = f->vote;
+  a.stable = rs->stable;
+  a.applied = rs->applied;
+  a.snap_pending = rs->snap_pending;
+  a.prev_term = rs->prev_term;
+  a.prev_commit = rs->prev_commit;
+  a.prev_vote = rs->prev_vote;
+  a.prev_lead = rs->prev_lead;
+  a.prev_state = rs->prev_state;
+  a.pending = in->pending;
+  a.cap = out->capacity;
+  a.o_group = out->group;
+  a.o_term = out->term;
+  a.o_commit = out->commit;
+  a.o_vote = out->vote;
+  a.o_lead = out->lead;
+  a.o_state = out->state;
+  a.o_flags = out->flags;
+  a.o_ent_first = out->ent_first;
+  a.o_ent_count = out->ent_count;
+  a.o_ent_last_term = out->ent_last_term;
+  a.o_apply_first = out->apply_first;
+  a.o_apply_count = out->apply_count;
+  a.o_snap_index = out->snap_index;
+  a.o_ent_len = out->ent_len;
+  a.o_ent_term = out->ent_term;
+  a.o_apply_len = out->apply_len;
+  a.o_apply_term = out->apply_term;
+  // the pair loads of the count pass: 16 B of every u64 row, 2 B of every byte row
+  a.vec = al(a.term, 16) && al(a.committed, 16) && al(a.last_index, 16) && al(a.run_first, 16) &&
+          al(a.stable, 16) && al(a.applied, 16) && al(a.snap_pending, 16) &&
+          al(a.prev_term, 16) && al(a.prev_commit, 16) && al(a.vote, 2) && al(a.lead, 2) &&
+          al(a.state, 2) && al(a.prev_vote, 2) && al(a.prev_lead, 2) && al(a.prev_state, 2) &&
+          al(a.pending, 2);
+  // scratch: offsets (u64, 8-B aligned at the start), then counts (u32), as qe_collect; the flags
+  uint64_t *offsets = static_cast<uint64_t *>(scratch);
+  a.offsets = offsets;
+  a.counts = reinterpret_cast<uint32_t *>(offsets + nb);
+  const uintptr_t fl = reinterpret_cast<uintptr_t>(scratch) + ready_flag_offset(p->num_groups);
+  a.flag = reinterpret_cast<uint8_t *>((fl + 15) & ~static_cast<uintptr_t>(15));
+  int s = dispatch_ready_count(a, st);
+  if (s) return s;
+  hipLaunchKernelGGL(k_collect_scan, dim3(1), dim3(1024), 0, st, a.counts, nb, offsets, out->count);
+  s = hip_status(hipGetLastError());
+  if (s) return s;
+  return dispatch_ready_fill(a, out->ent_runs, st);
+}
+
+int qe_advance(const qe_progress *p, const qe_follower *f, const qe_ready_state *rs,
+               const qe_ready_out *list, const qe_advance_opt *opt, uint8_t *result,
+               void *stream) {
+  const int rc = check_progress(p);
+  if (rc) return rc;
+  if (!rs || !list || !list->count || !result) return QE_EINVAL;
+  if (list->reserved || p->reserved3 || (opt && (opt->reserved[0] || opt->reserved[1])))
+    return QE_EINVAL;
+  if (missing_log_model(p) || missing_ready_state(rs)) return QE_EINVAL;
+  if (list->capacity && missing_ready_fields(list)) return QE_EINVAL;
+  const bool al_on = opt && opt->auto_leave;
+  if (al_on && (!opt->pending_conf_index || !f || !f->state)) return QE_EINVAL;
+  if (p->num_groups == 0 || list->capacity == 0) return QE_OK;
+  ADArgs a{};
+  a.G = p->num_groups;
+  a.goff = p->group_offset;
+  a.stride = p->stride;
+  a.cap = list->capacity;
+  a.R = p->log_runs;
+  a.S = p->num_slots;
+  a.count = list->count;
+  a.group = list->group;
+  a.term = list->term;
+  a.commit = list->commit;
+  a.vote = list->vote;
+  a.lead = list->lead;
+  a.state = list->state;
+  a.flags = list->flags;
+  a.ent_first = list->ent_first;
+  a.ent_count = list->ent_count;
+  a.ent_last_term = list->ent_last_term;
+  a.apply_first = list->apply_first;
+  a.apply_count = list->apply_count;
+  a.snap_index = list->snap_index;
+  a.committed = p->committed;
+  a.last_index = p->last_index;
+  a.run_first = p->run_first;
+  a.run_term = p->run_term;
+  a.run_count = p->run_count;
+  a.stable = rs->stable;
+  a.applied = rs->applied;
+  a.snap_pending = rs->snap_pending;
+  a.prev_term = rs->prev_term;
+  a.prev_commit = rs->prev_commit;
+  a.prev_vote = rs->prev_vote;
+  a.prev_lead = rs->prev_lead;
+  a.prev_state = rs->prev_state;
+  a.auto_leave = al_on ? opt->auto_leave : nullptr;
+  a.pending_conf_index = al_on ? opt->pending_conf_index : nullptr;
+  a.cur_state = al_on ? f->state : nullptr;
+  a.result = result;
+  return dispatch_advance(a, static_cast<hipStream_t>(stream));
 }
 
 size_t qe_inbox_scratch_bytes(uint64_t num_groups, uint32_t num_slots, uint64_t num_records) {

@@ -1236,6 +1236,141 @@ def replies(ps, term, rp, follow=None, snap=None, vote=None, timeout_now=None, f
     return rp
 
 
+class ReadyState(_Rows):
+    """The resident rows of qe_ready_state [G]: `stable` (unstable.offset - 1),
+    `applied`, `snap_pending` (0 = none), prev_term / prev_commit int64 storage
+    of the u64 rows, prev_vote / prev_lead / prev_state u8 (rn.prevHardSt and
+    rn.prevSoftSt; a slot >= S is None).  Pass the tensor qe_propose /
+    qe_compact read as `applied` to share the row."""
+
+    FIELDS = ("stable:u64 applied:u64 snap_pending:u64 prev_term:u64 prev_commit:u64 prev_vote:u8 "
+              "prev_lead:u8 prev_state:u8")
+
+    def __init__(self, ps, applied=None):
+        dev, i64, u8 = ps.device, torch.int64, torch.uint8
+        for k in ("stable", "snap_pending", "prev_term", "prev_commit"):
+            setattr(self, k, torch.zeros(ps.G, dtype=i64, device=dev))
+        self.applied = applied if applied is not None else torch.zeros(ps.G, dtype=i64, device=dev)
+        self.prev_vote = torch.full((ps.G,), 0xFF, dtype=u8, device=dev)
+        self.prev_lead = torch.full((ps.G,), 0xFF, dtype=u8, device=dev)
+        self.prev_state = torch.zeros(ps.G, dtype=u8, device=dev)
+
+    def reset(self, ps, fol):
+        """What NewRawNode does: prev := current, stable = last_index,
+        snap_pending = 0.  `applied` is the caller's."""
+        self.stable.copy_(ps.last_index)
+        self.snap_pending.zero_()
+        self.prev_term.copy_(fol.term)
+        self.prev_commit.copy_(ps.committed)
+        if fol.vote is None:
+            self.prev_vote.fill_(0xFF)
+        else:
+            self.prev_vote.copy_(fol.vote)
+        self.prev_lead.copy_(fol.lead)
+        self.prev_state.copy_(fol.state)
+        return self
+
+    def struct(self):
+        return _lib.QeReadyState(*[_ptr(getattr(self, k)) for k in self.ARRAYS])
+
+
+class Ready(_Rows):
+    """The record arrays of qe_ready (qe_ready_out) for up to `capacity`
+    groups: group / term / commit / ent_first / ent_count / ent_last_term /
+    apply_first / apply_count / snap_index int64 storage of the u64 fields,
+    vote / lead / state / flags u8 (QE_RD_*), the entries to persist and the
+    entries to apply as ent_runs term runs each (ent_len / apply_len int32,
+    ent_term / apply_term int64, [E][capacity]), and `count` (int64[1]): the
+    groups listed, which may exceed capacity.  The scratch of the call and the
+    result row of advance() are cached here."""
+
+    U64 = ("group", "term", "commit", "ent_first", "ent_count", "ent_last_term", "apply_first",
+           "apply_count", "snap_index")
+    FIELDS = ("group:u64 term:u64 commit:u64 vote:u8 lead:u8 state:u8 flags:u8 ent_first:u64 "
+              "ent_count:u64 ent_last_term:u64 apply_first:u64 apply_count:u64 snap_index:u64 "
+              "ent_len:u32? ent_term:u64? apply_len:u32? apply_term:u64? count:u64")
+    RUNS = ("ent_len", "ent_term", "apply_len", "apply_term")
+
+    def __init__(self, ps, capacity, ent_runs=_lib.QE_MAX_MSG_RUNS):
+        if not 0 <= int(ent_runs) <= _lib.QE_MAX_MSG_RUNS:
+            raise ValueError("ent_runs must be 0..QE_MAX_MSG_RUNS")
+        dev, i64, u8 = ps.device, torch.int64, torch.uint8
+        self.capacity, self.ent_runs = int(capacity), int(ent_runs)
+        n = max(1, self.capacity)
+        for k in self.U64:
+            setattr(self, k, torch.zeros(n, dtype=i64, device=dev))
+        for k in ("vote", "lead", "state", "flags"):
+            setattr(self, k, torch.zeros(n, dtype=u8, device=dev))
+        e = self.ent_runs * n
+        for k in self.RUNS:
+            dt = torch.int32 if k.endswith("len") else i64
+            setattr(self, k, torch.zeros(e, dtype=dt, device=dev) if e else None)
+        self.count = torch.zeros(1, dtype=i64, device=dev)
+        self.result = torch.zeros(n, dtype=u8, device=dev)
+        self.scratch = None
+
+    def struct(self):
+        return _lib.QeReadyOut(self.capacity, self.ent_runs, 0,
+                               *[_ptr(getattr(self, k)) for k in self.ARRAYS])
+
+    def records(self):
+        """-> (count, the rows cut to min(count, capacity) as numpy arrays; the
+        run rows as [E][n], None with ent_runs 0)."""
+        count = int(self.count.item())
+        n, cap = min(count, self.capacity), max(1, self.capacity)
+        h = self.host()
+        out = {k: h[k][:n] for k in self.ARRAYS if k not in self.RUNS and k != "count"}
+        for k in self.RUNS:
+            out[k] = None if h[k] is None else h[k].reshape(self.ent_runs, cap)[:, :n]
+        return count, out
+
+
+def ready_note(ps, rs, follow=None, snap=None):
+    """qe_ready_note: keep rs.stable / rs.snap_pending right after a
+    follower_step (follow = its FollowerOut) and / or a snapshot_step (snap =
+    its SnapOut)."""
+    i = _lib.QeReadyNoteIn()
+    if follow is not None:
+        i.follow_result, i.append_from = _ptr(follow.result), _ptr(follow.append_from)
+    if snap is not None:
+        i.snap_result, i.snap_resp_index = _ptr(snap.result), _ptr(snap.resp_index)
+    p, r = ps.struct(), rs.struct()
+    check("qe_ready_note", _lib.lib().qe_ready_note(C.byref(p), C.byref(r), C.byref(i),
+                                                    _stream(ps.device)))
+    return rs
+
+
+def ready(ps, fol, rs, rd, pending=None, max_apply=0, stats=None):
+    """qe_ready: HasReady + readyWithoutAccept over the batch -> the groups
+    that have something to persist or apply as a dense list in `rd`, by
+    ascending group.  `pending` [G] u8 marks groups to list whatever their
+    state (messages, ReadStates).  Nothing resident is written."""
+    lib = _lib.lib()
+    if rd.scratch is None:
+        rd.scratch = torch.empty((lib.qe_ready_scratch_bytes(ps.G) + 7) // 8 + 1,
+                                 dtype=torch.int64, device=ps.device)
+    p, f, r, o = ps.struct(), fol.struct(), rs.struct(), rd.struct()
+    i = _lib.QeReadyIn(_ptr(pending), int(max_apply), 0)
+    check("qe_ready", lib.qe_ready(C.byref(p), C.byref(f), C.byref(r), C.byref(i), C.byref(o),
+                                   _ptr(rd.scratch), _ptr(stats), _stream(ps.device)))
+    return rd
+
+
+def advance(ps, rs, rd, fol=None, auto_leave=None, pending_conf_index=None):
+    """qe_advance: acceptReady + RawNode.Advance + raft.advance for the records
+    of `rd` (a Ready as qe_ready left it, or one the host filled) -> rd.result,
+    one QE_ADV_* per record.  With auto_leave / pending_conf_index [G] and
+    `fol`, QE_ADV_AUTO_LEAVE marks the leaders that now append the leave-joint
+    entry."""
+    p, r, o = ps.struct(), rs.struct(), rd.struct()
+    f = fol.struct() if fol is not None else None
+    opt = _lib.QeAdvanceOpt(_ptr(auto_leave), _ptr(pending_conf_index))
+    check("qe_advance", _lib.lib().qe_advance(C.byref(p), C.byref(f) if f is not None else None,
+                                              C.byref(r), C.byref(o), C.byref(opt),
+                                              _ptr(rd.result), _stream(ps.device)))
+    return rd.result
+
+
 class Inbox(_Rows):
     """The record list of qe_inbox (qe_inbox_in) for up to `capacity` delivered
     messages, and the per-record outputs: group / term / index / log_term /

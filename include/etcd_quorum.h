@@ -2084,6 +2084,220 @@ size_t qe_replies_scratch_bytes(uint64_t num_groups);   /* == qe_collect_scratch
 int qe_replies(const qe_progress *p, const qe_replies_in *in, const qe_replies_out *out,
                void *scratch, uint64_t *stats, void *stream);
 
+/* qe_ready_note / qe_ready / qe_advance (additive in ABI 8): the storage half
+ * of RawNode.Ready() as a dense device list, and the Advance() that moves the
+ * cursors -- the half of a Ready that qe_outbox / qe_replies (Messages) do not
+ * list: the HardState and SoftState deltas, the entries to persist, the
+ * entries to apply, a pending snapshot and MustSync (raft/rawnode.go:133-179,
+ * raft/node.go:562-593, raft/log.go:170-197, raft/log_unstable.go).  A host
+ * asks "which groups have something to persist or apply, and what?" and copies
+ * min(*count, capacity) records instead of the G-sized term, vote, commit,
+ * lead, state and last_index rows.
+ *
+ * qe_ready_state, eight resident rows [G], read-write, device:
+ *   stable        unstable.offset - 1: every entry <= stable is in Storage
+ *   applied       raftLog.applied (the row qe_propose / qe_compact read)
+ *   snap_pending  index of unstable.snapshot, 0 = none
+ *   prev_term, prev_commit, prev_vote   rn.prevHardSt (vote as a slot, >=
+ *                 num_slots = None)
+ *   prev_lead, prev_state               rn.prevSoftSt (lead as a slot)
+ * NewRawNode: prev := current, stable = last_index, snap_pending = 0; applied
+ * is the caller's.  In every rule below a vote or lead >= num_slots is None,
+ * whatever its value: two different encodings of None are equal.
+ *
+ * qe_ready_note keeps unstable.offset right across receiver steps: it runs
+ * after a qe_follower_step and / or a qe_snapshot_step, on their own result
+ * rows (each pair of rows optional; of p it reads num_groups alone).
+ *   follow_result[g] == QE_FR_APP_ACCEPT && append_from[g] != 0:
+ *     stable = min(stable, append_from - 1) (unstable.truncateAndAppend,
+ *     log_unstable.go:121-141: only its `after <= offset` arm moves offset);
+ *   then snap_result[g] == QE_SR_RESTORED: stable = snap_pending =
+ *     snap_resp_index[g] (unstable.restore, :115-119).
+ * Leader-side appends (qe_propose, qe_become_leader) never truncate and need
+ * no note.  QE_EINVAL: a NULL p / rs / in / stable; one row of a pair without
+ * the other; snap_result with a NULL snap_pending.
+ *
+ * qe_ready: HasReady + readyWithoutAccept over the batch.  Of p it reads
+ * num_groups (G), group_offset, num_slots (S), stride, log_runs, committed,
+ * last_index, run_first, run_term, run_count; of f term, state, lead, vote (a
+ * NULL vote row: None everywhere); the rows of rs; in->pending.  It writes
+ * nothing resident.  Per group g:
+ *  1. hard = (term, vote, committed); hard_changed = hard != (prev_term,
+ *     prev_vote, prev_commit); hard_empty = term 0, vote None, committed 0.
+ *     soft = (lead, state); soft_changed = soft != (prev_lead, prev_state).
+ *  2. Entries = (stable, last_index]: ent_first = stable + 1 (in every
+ *     record).  With ent_runs E > 0 they are cut into the table's term runs
+ *     exactly as qe_outbox rule 4 cuts a MsgApp with index = stable: run j is
+ *     the j-th table run that overlaps the range, ent_len[j*capacity+i] its
+ *     overlap, ent_term[j*capacity+i] its term; the list ends after E runs and
+ *     QE_RD_ENTS_CUT is set when it ends below last_index.  ent_count = the
+ *     entries listed, ent_last_term = the term of the last listed entry (what
+ *     stableTo needs), 0 with none.  With E = 0 no runs are listed and the
+ *     range is whole: ent_count = last_index - stable, ent_last_term =
+ *     term(last_index).  The caller keeps run_first[0] <= stable (results are
+ *     unspecified otherwise; memory stays in bounds).
+ *  3. CommittedEntries (raftLog.nextEnts): off = max(applied + 1, run_first[0]
+ *     + 1); if committed + 1 > off they are [off, hi], hi = committed, or off +
+ *     max_apply - 1 when max_apply is nonzero and smaller (the entry-count
+ *     model of maxNextEntsSize, as max_ents models MaxSizePerMsg).  With E > 0
+ *     they are cut into term runs as the entries are (apply_len / apply_term,
+ *     a second [E][capacity] pair) and end after E runs.  apply_count = the
+ *     entries listed, apply_first = off (0 with apply_count 0);
+ *     QE_RD_APPLY_CUT is set when the list ends below committed.
+ *  4. Snapshot: snap_pending != 0 -> QE_RD_SNAP, snap_index = snap_pending.
+ *  5. MustSync (node.go:586-593) = Entries non-empty || vote != prev_vote ||
+ *     term != prev_term -> QE_RD_MUST_SYNC.
+ *  6. Listing.  g is listed iff soft_changed, or !hard_empty && hard_changed,
+ *     or snap_pending != 0, or Entries is non-empty, or CommittedEntries is
+ *     non-empty, or pending[g] != 0 (an optional row for what this call
+ *     cannot see: messages, which qe_outbox / qe_replies list, and
+ *     ReadStates).
+ *  7. Every listed record: group = group_offset + g, term, commit =
+ *     committed, vote and lead (0xFF for None), state, and flags: QE_RD_SOFT
+ *     where soft_changed, QE_RD_HARD where !hard_empty && hard_changed (only
+ *     then does a Ready carry the HardState), MUST_SYNC, SNAP and the two CUT
+ *     bits.  Unused run rows of a record are 0.
+ *  8. Order and truncation.  Records are listed by ascending g; *count is the
+ *     full number; nothing at or past min(*count, capacity) is touched in any
+ *     output array (qe_outbox rule 3).
+ *  9. stats (optional), over every listed group, those past capacity too:
+ *     QE_STAT_GROUPS += records; QE_STAT_READY_ENTRIES += ent_count;
+ *     QE_STAT_READY_APPLY += apply_count; QE_STAT_READY_MUST_SYNC += MustSync
+ *     records; QE_STAT_CHECKSUM += h9 per record, h1 = mix64(group *
+ *     0x9E3779B97F4A7C15 ^ 0x8CB92BA72F3D8DD7 ^ flags << 56 ^ vote << 48 ^ lead
+ *     << 40 ^ state << 32), then hk = mix64(hk-1 ^ x) over x = term, commit,
+ *     ent_first, ent_count, ent_last_term, apply_first, apply_count,
+ *     snap_index, as the record holds them.
+ * `count` and every array of qe_ready_out are DEVICE pointers; scratch is
+ * qe_ready_scratch_bytes(num_groups) bytes of device memory, 8-B aligned (the
+ * chunk offsets and counts of qe_collect and one flag byte per group).
+ * Stream-ordered: three kernels (count: one wave per 4096-group chunk, the
+ * scan of qe_collect, fill), no host synchronisation.
+ * QE_EINVAL: a NULL p / f / rs / in / out / count / scratch (with num_groups >
+ * 0); a NULL term, state or lead; a NULL committed, last_index, run_first,
+ * run_term or run_count; a NULL row of rs; stride < num_groups; num_slots
+ * outside 1..16; log_runs 0 or > QE_MAX_LOG_RUNS; ent_runs > QE_MAX_MSG_RUNS,
+ * or > 0 without ent_len / ent_term / apply_len / apply_term; capacity > 0
+ * with a NULL field array (group, term, commit, vote, lead, state, flags,
+ * ent_first, ent_count, ent_last_term, apply_first, apply_count, snap_index);
+ * a nonzero reserved field; scratch not 8-B aligned.  Every argument check
+ * runs before the first HIP call.  num_groups == 0 is QE_OK with *count = 0.
+ *
+ * qe_advance: acceptReady + RawNode.Advance + raft.advance (rawnode.go:
+ * 140-179, raft.go:543-580), driven by a record list in qe_ready's layout:
+ * `list` with its capacity, arrays and device count; n = min(*count,
+ * capacity) records, one thread each, so the work is n-sized, not G-sized.
+ * The run rows of the list are not read.  result[i] per record:
+ *  1. group - group_offset outside [0, G): QE_ADV_BAD_GROUP, nothing written.
+ *  2. newApplied = apply_first + apply_count - 1 when apply_count > 0, else
+ *     snap_index under QE_RD_SNAP, else 0 (Ready.appliedCursor).  newApplied >
+ *     0 and (committed < newApplied or newApplied < applied) is appliedTo's
+ *     panic: QE_ADV_APPLIED_RANGE, nothing of the group is written.  Otherwise
+ *     applied = newApplied (when > 0).
+ *  3. QE_RD_HARD: prev_term, prev_vote, prev_commit take the record's values.
+ *     QE_RD_SOFT: prev_lead, prev_state take the record's.
+ *  4. ent_count > 0: stableTo(i = ent_first + ent_count - 1, ent_last_term)
+ *     moves stable = i only when stable < i <= last_index and term(i) on the
+ *     run table equals ent_last_term; otherwise the outcome is
+ *     QE_ADV_OK_STALE_ENTRIES: the log was truncated under the Ready, and the
+ *     next qe_ready lists the entries again.
+ *  5. QE_RD_SNAP and snap_pending == snap_index: snap_pending = 0
+ *     (stableSnapTo).
+ *  6. With auto_leave (and then pending_conf_index and f->state, all [G]):
+ *     QE_ADV_AUTO_LEAVE is set in the result where newApplied > 0, auto_leave[g]
+ *     != 0, f->state[g] == QE_STATE_LEADER and applied-before <=
+ *     pending_conf_index[g] <= newApplied (raft.go:554).  The append itself
+ *     stays the caller's qe_propose with QE_PROP_APPEND_ONLY.
+ * result & QE_ADV_OUTCOME is QE_ADV_OK, _OK_STALE_ENTRIES, or a refusal (>=
+ * QE_ADV_REFUSED).  A group listed twice in one list is unspecified (memory
+ * stays in bounds); qe_ready never does it.  reduceUncommittedSize stays with
+ * the host, as for qe_propose.
+ * Of p it reads num_groups, group_offset, stride, log_runs, committed,
+ * last_index, run_first, run_term, run_count.  QE_EINVAL: a NULL p / rs / list
+ * / list->count / result; a NULL row of rs; a NULL log row of p; stride <
+ * num_groups; log_runs out of range; capacity > 0 with a NULL field array (as
+ * qe_ready's); a nonzero reserved field; auto_leave without
+ * pending_conf_index or f->state.  capacity == 0 or num_groups == 0 is QE_OK:
+ * nothing is written.
+ *
+ * DIVERGENCE from the reference: acceptReady is folded into qe_advance.
+ * RawNode.Ready() moves prevSoftSt at once; here a second qe_ready before the
+ * qe_advance lists the same SoftState again.
+ *
+ * With these calls the unstable / applied bookkeeping of a host (tests/
+ * trace_cluster.py Replay.ready / appended) is optional. */
+#define QE_RD_SOFT 1u        /* the record's lead / state are a SoftState delta */
+#define QE_RD_HARD 2u        /* the record's term / vote / commit are a HardState delta */
+#define QE_RD_MUST_SYNC 4u
+#define QE_RD_SNAP 8u        /* snap_index: the snapshot to persist and apply */
+#define QE_RD_ENTS_CUT 16u   /* the entries list ends below last_index */
+#define QE_RD_APPLY_CUT 32u  /* the apply list ends below committed */
+#define QE_ADV_OK 1
+#define QE_ADV_OK_STALE_ENTRIES 2
+#define QE_ADV_REFUSED 8          /* outcomes >= this: nothing of the group changed */
+#define QE_ADV_BAD_GROUP 8
+#define QE_ADV_APPLIED_RANGE 9
+#define QE_ADV_OUTCOME 0x0Fu
+#define QE_ADV_AUTO_LEAVE 0x10u   /* result bit: the leader appends the leave-joint entry */
+#define QE_STAT_READY_ENTRIES QE_STAT_COMMIT_SUM      /* qe_ready: entries listed */
+#define QE_STAT_READY_APPLY QE_STAT_COMMIT_ADVANCED   /* ... entries to apply */
+#define QE_STAT_READY_MUST_SYNC QE_STAT_VOTE_WON      /* ... records with MustSync */
+
+typedef struct qe_ready_state {
+  uint64_t *stable;               /* [G] rw */
+  uint64_t *applied;              /* [G] rw */
+  uint64_t *snap_pending;         /* [G] rw */
+  uint64_t *prev_term, *prev_commit;          /* [G] rw */
+  uint8_t  *prev_vote, *prev_lead, *prev_state; /* [G] rw */
+} qe_ready_state;
+
+typedef struct qe_ready_note_in {
+  const uint8_t  *follow_result;   /* [G] or NULL: qe_follower_out.result */
+  const uint64_t *append_from;     /* [G], with follow_result */
+  const uint8_t  *snap_result;     /* [G] or NULL: qe_snap_out.result */
+  const uint64_t *snap_resp_index; /* [G], with snap_result */
+} qe_ready_note_in;
+
+typedef struct qe_ready_in {
+  const uint8_t *pending;         /* [G] or NULL */
+  uint32_t max_apply;             /* entries to apply per record at most, 0 = no limit */
+  uint32_t reserved;              /* must be 0 */
+} qe_ready_in;
+
+typedef struct qe_ready_out {
+  uint64_t capacity;              /* records the arrays hold */
+  uint32_t ent_runs;              /* E, 0..QE_MAX_MSG_RUNS */
+  uint32_t reserved;
+  uint64_t *group;                /* [capacity] group_offset + g */
+  uint64_t *term, *commit;        /* [capacity] */
+  uint8_t  *vote, *lead, *state;  /* [capacity] */
+  uint8_t  *flags;                /* [capacity] QE_RD_* */
+  uint64_t *ent_first, *ent_count, *ent_last_term;   /* [capacity] */
+  uint64_t *apply_first, *apply_count;               /* [capacity] */
+  uint64_t *snap_index;           /* [capacity] */
+  uint32_t *ent_len;              /* [E][capacity] */
+  uint64_t *ent_term;             /* [E][capacity] */
+  uint32_t *apply_len;            /* [E][capacity] */
+  uint64_t *apply_term;           /* [E][capacity] */
+  uint64_t *count;                /* device: groups listed (may exceed capacity) */
+} qe_ready_out;
+
+typedef struct qe_advance_opt {
+  const uint8_t  *auto_leave;          /* [G] or NULL: Config.AutoLeave */
+  const uint64_t *pending_conf_index;  /* [G], with auto_leave */
+  uint32_t reserved[2];                /* must be 0 */
+} qe_advance_opt;
+
+int qe_ready_note(const qe_progress *p, const qe_ready_state *rs, const qe_ready_note_in *in,
+                  void *stream);
+size_t qe_ready_scratch_bytes(uint64_t num_groups);
+int qe_ready(const qe_progress *p, const qe_follower *f, const qe_ready_state *rs,
+             const qe_ready_in *in, const qe_ready_out *out, void *scratch, uint64_t *stats,
+             void *stream);
+/* f and opt may be NULL (no AutoLeave check). */
+int qe_advance(const qe_progress *p, const qe_follower *f, const qe_ready_state *rs,
+               const qe_ready_out *list, const qe_advance_opt *opt, uint8_t *result, void *stream);
+
 /* ---- statistics -------------------------------------------------------- */
 
 /* out[QE_STATS_COUNTERS] (device) = sum over shards of stats (device). */
