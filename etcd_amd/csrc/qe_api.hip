@@ -38,12 +38,6 @@ static inline bool al(const void *p, size_t a) {
   return (reinterpret_cast<uintptr_t>(p) % a) == 0;
 }
 
-static unsigned simple_grid(uint64_t G) {
-  const uint64_t cap = static_cast<uint64_t>(num_cus()) * 8;
-  const uint64_t need = (G + kBlock - 1) / kBlock;
-  return static_cast<unsigned>(need < cap ? (need ? need : 1) : cap);
-}
-
 // Sparse MsgAppResp acks: Progress.MaybeUpdate with 64-bit atomic max.
 __global__ __launch_bounds__(kBlock) void k_apply_acks(uint64_t G, uint32_t S, uint64_t stride,
                                                        uint64_t *match, uint64_t *next,
@@ -83,6 +77,29 @@ __global__ void k_stats_reduce(const uint64_t *stats, uint64_t *out) {
 // C ABI
 // ===========================================================================
 using namespace qe;
+
+// The scratch part every list call shares with qe_collect: the chunk offsets
+// (u64, so the scratch is 8-B aligned at the start), then the chunk counts (u32).
+static_assert(kListChunk == kCollectChunk && kIbChunk == kCollectChunk,
+              "k_collect_count's and k_collect_scan's chunks");
+struct ScanScratch {
+  int status;  // QE_OK; QE_ERANGE when the chunks pass the 2^31 - 1 blocks of a launch
+  uint64_t nb;  // chunks
+  uint64_t *offsets;
+  uint32_t *counts;
+};
+static ScanScratch scan_scratch(void *scratch, uint64_t n) {
+  const uint64_t nb = (n + kCollectChunk - 1) / kCollectChunk;
+  if (nb > 0x7FFFFFFFull) return {QE_ERANGE, 0, nullptr, nullptr};
+  uint64_t *offsets = static_cast<uint64_t *>(scratch);
+  return {QE_OK, nb, offsets, reinterpret_cast<uint32_t *>(offsets + nb)};
+}
+// k_collect_scan: the exclusive prefix of the chunk counts and the total.
+static int launch_scan(const ScanScratch &sc, uint64_t *total, hipStream_t st) {
+  hipLaunchKernelGGL(k_collect_scan, dim3(1), dim3(1024), 0, st, sc.counts, sc.nb, sc.offsets,
+                     total);
+  return hip_status(hipGetLastError());
+}
 
 // The head the argument struct of every step kernel (qe_follower_step, qe_vote_step,
 // qe_snapshot_step, qe_compact) starts with, and the statistics.
@@ -210,7 +227,7 @@ int qe_vote_result(const qe_groups *g, uint8_t *vote, void *stream) {
   if (g->num_groups == 0) return QE_OK;
   const uint32_t full = (1u << g->num_slots) - 1u;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const unsigned grid = simple_grid(g->num_groups);
+  const unsigned grid = elem_grid(g->num_groups, num_cus());
   if (g->num_slots <= 8)
     hipLaunchKernelGGL(k_vote_result<uint8_t>, dim3(grid), dim3(kBlock), 0, st, g->num_groups,
                        full, g->inc_mask, g->out_mask, g->voted, g->granted, vote);
@@ -229,7 +246,7 @@ int qe_quorum_active(const qe_groups *g, const void *recent_active, uint8_t *act
   if (g->num_groups == 0) return QE_OK;
   const uint32_t full = (1u << g->num_slots) - 1u;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const unsigned grid = simple_grid(g->num_groups);
+  const unsigned grid = elem_grid(g->num_groups, num_cus());
   if (g->num_slots <= 8)
     hipLaunchKernelGGL(k_quorum_active<uint8_t>, dim3(grid), dim3(kBlock), 0, st,
                        g->num_groups, full, g->inc_mask, g->out_mask, g->learner_mask,
@@ -248,7 +265,7 @@ int qe_record_votes(uint64_t num_groups, uint32_t num_slots, void *voted, void *
   if (!voted || !granted || !resp_mask || !resp_value) return QE_EINVAL;
   const uint32_t full = (1u << num_slots) - 1u;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const unsigned grid = simple_grid(num_groups);
+  const unsigned grid = elem_grid(num_groups, num_cus());
   if (num_slots <= 8)
     hipLaunchKernelGGL(k_record_votes<uint8_t>, dim3(grid), dim3(kBlock), 0, st, num_groups,
                        full, voted, granted, resp_mask, resp_value);
@@ -346,7 +363,7 @@ int qe_apply_append_resps(uint64_t num_groups, uint32_t num_slots, uint64_t stri
   if (num_slots == 0 || num_slots > QE_MAX_SLOTS) return QE_EINVAL;
   if (n == 0 || num_groups == 0) return QE_OK;
   if (stride < num_groups || !match || !next || !group || !slot || !index) return QE_EINVAL;
-  hipLaunchKernelGGL(k_apply_acks, dim3(simple_grid(n)), dim3(kBlock), 0,
+  hipLaunchKernelGGL(k_apply_acks, dim3(elem_grid(n, num_cus())), dim3(kBlock), 0,
                      static_cast<hipStream_t>(stream), num_groups, num_slots, stride, match,
                      next, n, group, slot, index, touched);
   return hip_status(hipGetLastError());
@@ -955,23 +972,20 @@ int qe_collect(uint64_t num_groups, uint64_t group_offset, const uint64_t *perm,
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (num_groups == 0)
     return hip_status(hipMemsetAsync(out_count, 0, sizeof(uint64_t), st));
-  const uint64_t nb = (num_groups + kCollectChunk - 1) / kCollectChunk;
-  if (nb > 0x7FFFFFFFull) return QE_ERANGE;
-  // scratch: offsets (u64, 8-B aligned at the start), then counts (u32)
-  if (reinterpret_cast<uintptr_t>(scratch) % 8) return QE_EINVAL;
-  uint64_t *offsets = static_cast<uint64_t *>(scratch);
-  uint32_t *counts = reinterpret_cast<uint32_t *>(offsets + nb);
-  const bool vec = (reinterpret_cast<uintptr_t>(flags) % 16) == 0;
+  const ScanScratch sc = scan_scratch(scratch, num_groups);
+  if (sc.status) return sc.status;
+  if (!al(scratch, 8)) return QE_EINVAL;
+  const uint64_t nb = sc.nb;
+  const bool vec = al(flags, 16);
   hipLaunchKernelGGL(k_collect_count, dim3(static_cast<unsigned>((nb + kCountWaves - 1) / kCountWaves)),
-                     dim3(kBlock), 0, st, flags, num_groups, vec, nb, counts);
-  hipLaunchKernelGGL(k_collect_scan, dim3(1), dim3(1024), 0, st, counts, nb, offsets, out_count);
+                     dim3(kBlock), 0, st, flags, num_groups, vec, nb, sc.counts);
+  if (const int s = launch_scan(sc, out_count, st)) return s;
   hipLaunchKernelGGL(k_collect_scatter, dim3(static_cast<unsigned>(nb)), dim3(kBlock), 0, st, flags,
-                     num_groups, vec, group_offset, perm, values, offsets, out_groups, out_values);
+                     num_groups, vec, group_offset, perm, values, sc.offsets, out_groups, out_values);
   return hip_status(hipGetLastError());
 }
 
 size_t qe_outbox_scratch_bytes(uint64_t num_groups) {
-  static_assert(kObChunk == kCollectChunk, "k_collect_scan's chunks");
   return qe_collect_scratch_bytes(num_groups);
 }
 
@@ -992,9 +1006,9 @@ int qe_outbox(const qe_progress *p, const qe_outbox_in *in, const qe_outbox_out 
   if (out->capacity && (!out->group || !out->to || !out->type || !out->term || !out->index ||
                         !out->log_term || !out->commit))
     return QE_EINVAL;
-  if (p->num_groups && (!scratch || reinterpret_cast<uintptr_t>(scratch) % 8)) return QE_EINVAL;
-  const uint64_t nb = (p->num_groups + kObChunk - 1) / kObChunk;
-  if (nb > 0x7FFFFFFFull) return QE_ERANGE;
+  if (p->num_groups && (!scratch || !al(scratch, 8))) return QE_EINVAL;
+  const ScanScratch sc = scan_scratch(scratch, p->num_groups);
+  if (sc.status) return sc.status;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (p->num_groups == 0) return hip_status(hipMemsetAsync(out->count, 0, sizeof(uint64_t), st));
   OBArgs a{};
@@ -1002,7 +1016,9 @@ int qe_outbox(const qe_progress *p, const qe_outbox_in *in, const qe_outbox_out 
   a.S = p->num_slots;
   a.wide = p->num_slots > 8;
   a.max_entries = in->max_entries;
-  a.nb = nb;
+  a.nb = sc.nb;
+  a.offsets = sc.offsets;
+  a.counts = sc.counts;
   a.sent = in->sent;
   a.snap = in->snap;
   a.hb_sent = in->hb_sent;
@@ -1032,20 +1048,15 @@ int qe_outbox(const qe_progress *p, const qe_outbox_in *in, const qe_outbox_out 
   a.o_ctx = out->ctx;
   a.o_ent_len = out->ent_len;
   a.o_ent_term = out->ent_term;
-  // scratch: offsets (u64, 8-B aligned at the start), then counts (u32), as qe_collect
-  uint64_t *offsets = static_cast<uint64_t *>(scratch);
-  a.offsets = offsets;
-  a.counts = reinterpret_cast<uint32_t *>(offsets + nb);
   int s = dispatch_outbox_count(a, st);
   if (s) return s;
-  hipLaunchKernelGGL(k_collect_scan, dim3(1), dim3(1024), 0, st, a.counts, nb, offsets, out->count);
-  s = hip_status(hipGetLastError());
+  s = launch_scan(sc, out->count, st);
   if (s) return s;
   return dispatch_outbox_fill(a, out->msg_runs, st);
 }
 
 size_t qe_replies_scratch_bytes(uint64_t num_groups) {
-  return qe_collect_scratch_bytes(num_groups);  // (kObChunk: qe_outbox_scratch_bytes)
+  return qe_collect_scratch_bytes(num_groups);
 }
 
 int qe_replies(const qe_progress *p, const qe_replies_in *in, const qe_replies_out *out,
@@ -1065,9 +1076,9 @@ int qe_replies(const qe_progress *p, const qe_replies_in *in, const qe_replies_o
   if (out->capacity && (!out->group || !out->to || !out->type || !out->term || !out->index ||
                         !out->log_term || !out->hint))
     return QE_EINVAL;
-  if (reinterpret_cast<uintptr_t>(scratch) % 8 || (p->num_groups && !scratch)) return QE_EINVAL;
-  const uint64_t nb = (p->num_groups + kObChunk - 1) / kObChunk;
-  if (nb > 0x7FFFFFFFull) return QE_ERANGE;
+  if (!al(scratch, 8) || (p->num_groups && !scratch)) return QE_EINVAL;
+  const ScanScratch sc = scan_scratch(scratch, p->num_groups);
+  if (sc.status) return sc.status;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (p->num_groups == 0 ||
       (!in->f_result && !in->s_result && !in->v_result && !in->timeout_now))
@@ -1077,7 +1088,9 @@ int qe_replies(const qe_progress *p, const qe_replies_in *in, const qe_replies_o
   a.goff = p->group_offset;
   a.S = p->num_slots;
   a.wide = p->num_slots > 8;
-  a.nb = nb;
+  a.nb = sc.nb;
+  a.offsets = sc.offsets;
+  a.counts = sc.counts;
   a.term = in->term;
   a.f_result = in->f_result;
   a.f_from = in->f_from;
@@ -1107,14 +1120,9 @@ int qe_replies(const qe_progress *p, const qe_replies_in *in, const qe_replies_o
   a.o_ctx = out->ctx;
   a.o_flags = out->flags;
   a.stats = stats;
-  // scratch: offsets (u64, 8-B aligned at the start), then counts (u32), as qe_collect
-  uint64_t *offsets = static_cast<uint64_t *>(scratch);
-  a.offsets = offsets;
-  a.counts = reinterpret_cast<uint32_t *>(offsets + nb);
   int s = dispatch_replies_count(a, st);
   if (s) return s;
-  hipLaunchKernelGGL(k_collect_scan, dim3(1), dim3(1024), 0, st, a.counts, nb, offsets, out->count);
-  s = hip_status(hipGetLastError());
+  s = launch_scan(sc, out->count, st);
   if (s) return s;
   return dispatch_replies_fill(a, st);
 }
@@ -1155,7 +1163,6 @@ static size_t ready_flag_offset(uint64_t num_groups) {
 }
 
 size_t qe_ready_scratch_bytes(uint64_t num_groups) {
-  static_assert(kObChunk == kCollectChunk, "k_collect_scan's chunks");
   return ready_flag_offset(num_groups) + static_cast<size_t>(num_groups) + 16;
 }
 
@@ -1171,16 +1178,18 @@ int qe_ready(const qe_progress *p, const qe_follower *f, const qe_ready_state *r
       (out->ent_runs && (!out->ent_len || !out->ent_term || !out->apply_len || !out->apply_term)))
     return QE_EINVAL;
   if (out->capacity && missing_ready_fields(out)) return QE_EINVAL;
-  if (reinterpret_cast<uintptr_t>(scratch) % 8 || (p->num_groups && !scratch)) return QE_EINVAL;
-  const uint64_t nb = (p->num_groups + kObChunk - 1) / kObChunk;
-  if (nb > 0x7FFFFFFFull) return QE_ERANGE;
+  if (!al(scratch, 8) || (p->num_groups && !scratch)) return QE_EINVAL;
+  const ScanScratch sc = scan_scratch(scratch, p->num_groups);
+  if (sc.status) return sc.status;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (p->num_groups == 0) return hip_status(hipMemsetAsync(out->count, 0, sizeof(uint64_t), st));
   RDArgs a{};
   step_head(p, stats, a);
   a.S = p->num_slots;
   a.max_apply = in->max_apply;
-  a.nb = nb;
+  a.nb = sc.nb;
+  a.offsets = sc.offsets;
+  a.counts = sc.counts;
   a.committed = p->committed;
   a.last_index = p->last_index;
   a.run_first = p->run_first;
@@ -1223,16 +1232,12 @@ int qe_ready(const qe_progress *p, const qe_follower *f, const qe_ready_state *r
           al(a.prev_term, 16) && al(a.prev_commit, 16) && al(a.vote, 2) && al(a.lead, 2) &&
           al(a.state, 2) && al(a.prev_vote, 2) && al(a.prev_lead, 2) && al(a.prev_state, 2) &&
           al(a.pending, 2);
-  // scratch: offsets (u64, 8-B aligned at the start), then counts (u32), as qe_collect; the flags
-  uint64_t *offsets = static_cast<uint64_t *>(scratch);
-  a.offsets = offsets;
-  a.counts = reinterpret_cast<uint32_t *>(offsets + nb);
+  // the flags, behind the offsets and the counts
   const uintptr_t fl = reinterpret_cast<uintptr_t>(scratch) + ready_flag_offset(p->num_groups);
   a.flag = reinterpret_cast<uint8_t *>((fl + 15) & ~static_cast<uintptr_t>(15));
   int s = dispatch_ready_count(a, st);
   if (s) return s;
-  hipLaunchKernelGGL(k_collect_scan, dim3(1), dim3(1024), 0, st, a.counts, nb, offsets, out->count);
-  s = hip_status(hipGetLastError());
+  s = launch_scan(sc, out->count, st);
   if (s) return s;
   return dispatch_ready_fill(a, out->ent_runs, st);
 }
@@ -1292,7 +1297,6 @@ int qe_advance(const qe_progress *p, const qe_follower *f, const qe_ready_state 
 }
 
 size_t qe_inbox_scratch_bytes(uint64_t num_groups, uint32_t num_slots, uint64_t num_records) {
-  static_assert(kIbChunk == kCollectChunk, "k_collect_count's and k_collect_scan's chunks");
   if (num_slots == 0 || num_slots > QE_MAX_SLOTS) return 0;
   return static_cast<size_t>(4 * (3 + static_cast<uint64_t>(num_slots)) * num_groups +
                              num_records + qe_collect_scratch_bytes(num_records));
@@ -1319,7 +1323,7 @@ int qe_inbox(const qe_progress *p, const qe_follower *f, const qe_inbox_in *in,
       !out->disposition || !out->deferred || !out->deferred_count)
     return QE_EINVAL;
   if (p->num_groups && !scratch) return QE_EINVAL;
-  if (reinterpret_cast<uintptr_t>(scratch) % 8) return QE_EINVAL;
+  if (!al(scratch, 8)) return QE_EINVAL;
   if (n > 0xFFFFFFF0ull) return QE_ERANGE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (p->num_groups == 0)
@@ -1377,12 +1381,11 @@ int qe_inbox(const qe_progress *p, const qe_follower *f, const qe_inbox_in *in,
   a.disposition = out->disposition;
   a.deferred = out->deferred;
   a.stats = stats;
-  // scratch: qe_collect's part for n flags (offsets u64, 8-B aligned at the start, then counts
-  // u32), the words first / stop / hi [G] and cell [S][G], the flags [n]
-  const uint64_t nb = (n + kIbChunk - 1) / kIbChunk;
-  uint64_t *offsets = static_cast<uint64_t *>(scratch);
-  uint32_t *counts = reinterpret_cast<uint32_t *>(offsets + nb);
-  a.offsets = offsets;
+  // scratch: qe_collect's part for n flags (n is in range: its chunks fit a launch), the
+  // words first / stop / hi [G] and cell [S][G], the flags [n]
+  const ScanScratch sc = scan_scratch(scratch, n);
+  const uint64_t nb = sc.nb;
+  a.offsets = sc.offsets;
   a.first = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(scratch) +
                                          qe_collect_scratch_bytes(n));
   a.stop = a.first + a.G;
@@ -1396,11 +1399,9 @@ int qe_inbox(const qe_progress *p, const qe_follower *f, const qe_inbox_in *in,
     if (s) return s;
     const bool vec = (reinterpret_cast<uintptr_t>(a.dflag) % 16) == 0;
     hipLaunchKernelGGL(k_collect_count, dim3(static_cast<unsigned>((nb + kCountWaves - 1) / kCountWaves)),
-                       dim3(kBlock), 0, st, a.dflag, n, vec, nb, counts);
+                       dim3(kBlock), 0, st, a.dflag, n, vec, nb, sc.counts);
   }
-  hipLaunchKernelGGL(k_collect_scan, dim3(1), dim3(1024), 0, st, counts, nb, offsets,
-                     out->deferred_count);
-  s = hip_status(hipGetLastError());
+  s = launch_scan(sc, out->deferred_count, st);
   if (s || !n) return s;
   return dispatch_inbox_deferred(a, nb, st);
 }
@@ -1434,7 +1435,7 @@ int qe_gen_groups(const qe_groups *g, const qe_gen_params *p, void *stream) {
   // qe_gen_params.group_offset adds to qe_groups.group_offset.
   a.goff = g->group_offset + p->group_offset;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const unsigned grid = simple_grid(g->num_groups);
+  const unsigned grid = elem_grid(g->num_groups, num_cus());
   if (g->num_slots <= 8)
     hipLaunchKernelGGL(k_gen<uint8_t>, dim3(grid), dim3(kBlock), 0, st, a);
   else

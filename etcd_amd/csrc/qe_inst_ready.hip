@@ -13,8 +13,8 @@ __global__ __launch_bounds__(kBlock) void k_ready_count(RDArgs a) {
   const uint64_t c =
       static_cast<uint64_t>(blockIdx.x) * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (c >= a.nb) return;  // (wave-uniform)
-  const uint64_t base = c * kObChunk;
-  const uint32_t nc = static_cast<uint32_t>(a.G - base < kObChunk ? a.G - base : kObChunk);
+  const uint64_t base = c * kListChunk;
+  const uint32_t nc = static_cast<uint32_t>(a.G - base < kListChunk ? a.G - base : kListChunk);
   const rsrc_t r_term = mk_rsrc(a.term + base, nc * 8), r_com = mk_rsrc(a.committed + base, nc * 8),
                r_li = mk_rsrc(a.last_index + base, nc * 8), r_rf = mk_rsrc(a.run_first + base, nc * 8),
                r_stb = mk_rsrc(a.stable + base, nc * 8), r_app = mk_rsrc(a.applied + base, nc * 8),
@@ -27,9 +27,9 @@ __global__ __launch_bounds__(kBlock) void k_ready_count(RDArgs a) {
                r_pend = opt_rsrc(a.pending, base, nc), r_flag = mk_rsrc(a.flag + base, nc);
   const uint32_t novote = a.vote ? 0u : 0xFFu;  // a NULL vote row: None
   uint32_t cnt = 0;
-  if (a.vec && nc == kObChunk) {
+  if (a.vec && nc == kListChunk) {
 #pragma unroll 2
-    for (uint32_t j = 0; j < kObChunk / 128; j++) {
+    for (uint32_t j = 0; j < kListChunk / 128; j++) {
       const uint32_t q = j * 64 + lane;  // the pair of groups 2q, 2q + 1
       const u32x4 term = bld128(r_term, q * 16), com = bld128(r_com, q * 16),
                   li = bld128(r_li, q * 16), rf = bld128(r_rf, q * 16),
@@ -57,7 +57,7 @@ __global__ __launch_bounds__(kBlock) void k_ready_count(RDArgs a) {
       bst16(f2, r_flag, q * 2);
     }
   } else {
-    for (uint32_t j = 0; j < kObChunk / 64; j++) {
+    for (uint32_t j = 0; j < kListChunk / 64; j++) {
       const uint32_t i = j * 64 + lane, o8 = i * 8;  // past nc: out of range, reads 0
       if (__builtin_amdgcn_readfirstlane(j * 64) >= nc) break;
       const uint32_t f = rd_flags(
@@ -151,15 +151,8 @@ __global__ __launch_bounds__(kBlock) void k_advance(ADArgs a) {
   }
 }
 
-// A thread per element, at most 8 blocks per CU: the blocks walk.
-static dim3 walk_grid(uint64_t n) {
-  const uint64_t cap = static_cast<uint64_t>(num_cus()) * 8;
-  const uint64_t need = (n + kBlock - 1) / kBlock;
-  return dim3(static_cast<unsigned>(need < cap ? (need ? need : 1) : cap));
-}
-
 int dispatch_ready_note(const RNArgs &a, hipStream_t st) {
-  hipLaunchKernelGGL(k_ready_note, walk_grid(a.G), dim3(kBlock), 0, st, a);
+  hipLaunchKernelGGL(k_ready_note, dim3(elem_grid(a.G, num_cus())), dim3(kBlock), 0, st, a);
   return hip_status(hipGetLastError());
 }
 
@@ -170,36 +163,20 @@ int dispatch_ready_count(const RDArgs &a, hipStream_t st) {
   return hip_status(hipGetLastError());
 }
 
-template <int RM>
-static void launch_fill(const RDArgs &a, uint32_t ent_runs, dim3 grid, hipStream_t st) {
-  static_assert(QE_MAX_MSG_RUNS == 4, "one case per run capacity of the lists");
-  switch (ent_runs) {
-    case 0: hipLaunchKernelGGL((k_ready_fill<RM, 0>), grid, dim3(kBlock), 0, st, a); break;
-    case 1: hipLaunchKernelGGL((k_ready_fill<RM, 1>), grid, dim3(kBlock), 0, st, a); break;
-    case 2: hipLaunchKernelGGL((k_ready_fill<RM, 2>), grid, dim3(kBlock), 0, st, a); break;
-    case 3: hipLaunchKernelGGL((k_ready_fill<RM, 3>), grid, dim3(kBlock), 0, st, a); break;
-    default: hipLaunchKernelGGL((k_ready_fill<RM, 4>), grid, dim3(kBlock), 0, st, a); break;
-  }
-}
-
-// One block per chunk; with statistics the grid is capped at 8 blocks per CU
-// and the blocks walk, since every wave ends with one atomic per counter.
 int dispatch_ready_fill(const RDArgs &a, uint32_t ent_runs, hipStream_t st) {
-  const uint64_t cap = a.stats ? static_cast<uint64_t>(num_cus()) * 8 : a.nb;
-  const dim3 grid(static_cast<unsigned>(a.nb < cap ? a.nb : cap));
-  if (a.R <= 4)
-    launch_fill<4>(a, ent_runs, grid, st);
-  else if (a.R <= 8)
-    launch_fill<8>(a, ent_runs, grid, st);
-  else
-    launch_fill<16>(a, ent_runs, grid, st);
-  return hip_status(hipGetLastError());
+  const dim3 grid(list_fill_grid(a.nb, num_cus(), a.stats != nullptr));
+  return with_run_bucket(a.R, [&](auto rm) {
+    return with_msg_runs(ent_runs, [&](auto e) {
+      hipLaunchKernelGGL((k_ready_fill<rm(), e()>), grid, dim3(kBlock), 0, st, a);
+      return hip_status(hipGetLastError());
+    });
+  });
 }
 
 // The count is on the device: the grid covers the capacity and a thread past
 // the count leaves at once.
 int dispatch_advance(const ADArgs &a, hipStream_t st) {
-  hipLaunchKernelGGL(k_advance, walk_grid(a.cap), dim3(kBlock), 0, st, a);
+  hipLaunchKernelGGL(k_advance, dim3(elem_grid(a.cap, num_cus())), dim3(kBlock), 0, st, a);
   return hip_status(hipGetLastError());
 }
 

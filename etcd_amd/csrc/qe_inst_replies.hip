@@ -15,11 +15,8 @@ int dispatch_replies_count(const RPArgs &a, hipStream_t st) {
   return hip_status(hipGetLastError());
 }
 
-// One block per chunk; with statistics the grid is capped at 8 blocks per CU
-// and the blocks walk, since every wave ends with one atomic per counter.
 int dispatch_replies_fill(const RPArgs &a, hipStream_t st) {
-  const uint64_t cap = a.stats ? static_cast<uint64_t>(num_cus()) * 8 : a.nb;
-  const dim3 grid(static_cast<unsigned>(a.nb < cap ? a.nb : cap));
+  const dim3 grid(list_fill_grid(a.nb, num_cus(), a.stats != nullptr));
   if (a.wide)
     hipLaunchKernelGGL(k_replies_fill<true>, grid, dim3(kBlock), 0, st, a);
   else

@@ -58,6 +58,23 @@ inline uint32_t tile_grid(uint64_t groups, int cus, bool stats) {
   return static_cast<uint32_t>(blocks ? blocks : 1);
 }
 
+// The grid of a record list's fill pass (qe_list.hpp): one block per chunk;
+// with statistics it is capped at 8 blocks per CU and the blocks walk, since
+// every wave ends with one atomic per counter.  The caller has checked that
+// the chunks fit a launch.
+inline uint32_t list_fill_grid(uint64_t chunks, int cus, bool stats) {
+  const uint64_t cap = stats ? static_cast<uint64_t>(cus) * 8 : chunks;
+  return static_cast<uint32_t>(chunks < cap ? chunks : cap);
+}
+
+// The grid of an element-wise kernel: a thread per element, at least one
+// block and at most 8 per CU (the blocks walk).
+inline uint32_t elem_grid(uint64_t n, int cus) {
+  const uint64_t cap = static_cast<uint64_t>(cus) * 8;
+  const uint64_t need = (n + kBlock - 1) / kBlock;
+  return static_cast<uint32_t>(need < cap ? (need ? need : 1) : cap);
+}
+
 // The three quorum forms the kernels are built for: f(MASKED, JOINT) with
 // std::bool_constant arguments — a plain majority of every slot, a majority
 // of inc_mask, or the joint quorum of inc_mask and out_mask.
@@ -105,6 +122,33 @@ inline int with_slots(uint32_t S, F &&f) {
     case 15: return f(slots_c<15>{});
     case 16: return f(slots_c<16>{});
     default: return QE_EINVAL;
+  }
+}
+
+template <int N>
+using runs_c = std::integral_constant<int, N>;
+
+// Dispatch by the run-capacity bucket of a kernel that holds the run table in
+// registers: f(runs_c<RM>) for the first RM of 4, 8, 16 that log_runs fits.
+template <class F>
+inline int with_run_bucket(uint32_t log_runs, F &&f) {
+  static_assert(QE_MAX_LOG_RUNS == 16, "the last bucket holds every run table");
+  if (log_runs <= 4) return f(runs_c<4>{});
+  if (log_runs <= 8) return f(runs_c<8>{});
+  return f(runs_c<16>{});
+}
+
+// Dispatch by the run capacity of a record (msg_runs, ent_runs): f(runs_c<E>)
+// for E in 0..QE_MAX_MSG_RUNS; the caller has refused a larger one.
+template <class F>
+inline int with_msg_runs(uint32_t runs, F &&f) {
+  static_assert(QE_MAX_MSG_RUNS == 4, "one case per run capacity");
+  switch (runs) {
+    case 0: return f(runs_c<0>{});
+    case 1: return f(runs_c<1>{});
+    case 2: return f(runs_c<2>{});
+    case 3: return f(runs_c<3>{});
+    default: return f(runs_c<4>{});
   }
 }
 

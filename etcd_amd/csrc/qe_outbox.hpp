@@ -6,35 +6,23 @@
 // message of a bit carries.  Everything a record needs is resident: the masks,
 // msg_index or Next, the term-run log, committed, the sender's term.
 //
-// Three passes over 4096-group chunks (64 tiles, a block of four waves each):
-//   count   k_outbox_count: the records of a chunk, from the masks alone;
-//   scan    k_collect_scan (qe_collect.hpp, launched by qe_outbox): the chunk
-//           offsets and the total;
-//   fill    k_outbox_fill: a block recounts its chunk's tiles from the mask
-//           bytes (64 words of LDS, the only LDS here), a wave scans them, and
-//           wave w writes the tiles 4k + w.  No block waits for another.
-// A tile in the house idiom (qe_step.hpp): one lane per group; the masks, then
-// term, the log's header and run table, snap_index and hb_ctx once per tile
-// under the ballot of the lanes that need them; then the per-slot rows (index,
-// or peer and next_before / next; hb_commit) of every slot in the tile's mask
-// union; then, slot by slot, the records.  The records of a slot take
-// consecutive positions in lane order (ballot + mbcnt; the slot's base is the
-// popcount of the earlier slots' ballots), so a wave's stores for one slot are
-// one contiguous run.  Every store follows every load of the tile.  Capacity is
-// the output descriptors' num_records: a record past it is an out-of-range
-// store, dropped, with no branch.  Every access is non-temporal.
+// The three passes of the record-list layer (qe_list.hpp): k_outbox_count
+// counts a chunk's records from the masks alone, k_outbox_fill recounts its
+// chunk's tiles from the mask bytes and fills them.
+// A tile: one lane per group; the masks, then term, the log's header and run
+// table, snap_index and hb_ctx once per tile under the ballot of the lanes that
+// need them; then the per-slot rows (index, or peer and next_before / next;
+// hb_commit) of every slot in the tile's mask union; then, slot by slot, the
+// records (the slot's base is the popcount of the earlier slots' ballots).
 //
 // RM is the run-capacity bucket (log_runs <= 4 / 8 / 16, as k_compact), E the
 // message's run capacity (qe_outbox_out.msg_runs).  The slot count and the mask
 // width are run-time values: one object, not one per QE_S.
 #pragma once
-#include "qe_step.hpp"
+#include "qe_list.hpp"
 
 namespace qe {
 
-constexpr uint32_t kObRounds = 16;                    // groups per thread and chunk
-constexpr uint32_t kObChunk = kBlock * kObRounds;     // groups per chunk (qe_collect's)
-constexpr uint32_t kObTiles = kObChunk / 64;          // tiles per chunk
 constexpr uint32_t kObTileMax = 64 * QE_MAX_SLOTS;    // records of one tile at most
 constexpr uint64_t kOutboxSalt = 0xC2B2AE3D27D4EB4Full;
 
@@ -72,59 +60,29 @@ struct OBArgs {
 int dispatch_outbox_count(const OBArgs &a, hipStream_t st);
 int dispatch_outbox_fill(const OBArgs &a, uint32_t msg_runs, hipStream_t st);
 
-// `cnt` elements of a mask-typed array from element `first` on (NULL: reads 0).
-__device__ __forceinline__ rsrc_t ob_mask_rsrc(const void *p, uint64_t first, uint32_t cnt,
-                                               uint32_t sz) {
-  return p ? mk_rsrc(static_cast<const uint8_t *>(p) + first * sz, cnt * sz) : mk_rsrc(p, 0);
-}
-__device__ __forceinline__ uint32_t ob_ld_mask(rsrc_t r, uint32_t i, bool wide) {
-  return wide ? bld16<kNT>(r, i * 2) : bld8<kNT>(r, i);
-}
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t x) {
+// The counts of the layer: the three masks of a thread's groups, the rounds'
+// loads independent and in flight together.  `wide`: the masks are 16-bit words.
+struct OutboxCounts {
+  const OBArgs &a;
+  bool wide;
+  __device__ __forceinline__ void operator()(uint64_t base, uint32_t nc,
+                                             uint32_t (&k)[kListRounds]) const {
+    const uint32_t sz = wide ? 2u : 1u, full = (1u << a.S) - 1u;
+    const rsrc_t rs = list_mask_rsrc(a.sent, base, nc, sz),
+                 rp = list_mask_rsrc(a.snap, base, nc, sz),
+                 rh = list_mask_rsrc(a.hb_sent, base, nc, sz);
 #pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
-  return x;
-}
-__device__ __forceinline__ uint32_t lane_rank(uint64_t bal) {
-  return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(bal >> 32),
-                                   __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(bal), 0u));
-}
-
-// The records of each tile of chunk c into tcnt[kObTiles]: thread t takes the
-// groups r * kBlock + t, so round r of wave w is tile 4r + w; the rounds'
-// loads are independent and in flight together.
-__device__ __forceinline__ void chunk_tile_counts(const OBArgs &a, bool wide, uint64_t c,
-                                                  uint32_t *tcnt) {
-  const uint32_t tid = threadIdx.x, lane = tid & 63;
-  const uint32_t w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const uint64_t base = c * kObChunk;
-  const uint32_t nc = static_cast<uint32_t>(a.G - base < kObChunk ? a.G - base : kObChunk);
-  const uint32_t sz = wide ? 2u : 1u, full = (1u << a.S) - 1u;
-  const rsrc_t rs = ob_mask_rsrc(a.sent, base, nc, sz), rp = ob_mask_rsrc(a.snap, base, nc, sz),
-               rh = ob_mask_rsrc(a.hb_sent, base, nc, sz);
-  uint32_t m[kObRounds];
-#pragma unroll
-  for (uint32_t r = 0; r < kObRounds; r++) {
-    const uint32_t i = r * kBlock + tid;  // past nc: out of range, reads 0
-    m[r] = ob_ld_mask(rs, i, wide) | ob_ld_mask(rp, i, wide) | ob_ld_mask(rh, i, wide);
+    for (uint32_t r = 0; r < kListRounds; r++) {
+      const uint32_t i = list_elem(r);
+      k[r] = popc((list_ld_mask(rs, i, wide) | list_ld_mask(rp, i, wide) |
+                   list_ld_mask(rh, i, wide)) & full);
+    }
   }
-#pragma unroll
-  for (uint32_t r = 0; r < kObRounds; r++) {
-    const uint32_t s = wave_sum_u32(popc(m[r] & full));
-    if (lane == 0) tcnt[r * (kBlock / 64) + w] = s;
-  }
-}
+};
 
-// One block per chunk.  WIDE: the masks are 16-bit words.
 template <bool WIDE>
 __global__ __launch_bounds__(kBlock) void k_outbox_count(OBArgs a) {
-  __shared__ uint32_t tcnt[kObTiles];
-  chunk_tile_counts(a, WIDE, blockIdx.x, tcnt);
-  __syncthreads();
-  if (threadIdx.x < 64) {
-    const uint32_t s = wave_sum_u32(tcnt[threadIdx.x]);
-    if (threadIdx.x == 0) a.counts[blockIdx.x] = s;
-  }
+  list_count_block(a.G, a.counts, OutboxCounts{a, WIDE});
 }
 
 enum { O_GROUPS, O_APP, O_SNAP, O_HB, O_BAD, O_VIOL, O_ENTRIES, O_CSUM, O_N };
@@ -136,9 +94,9 @@ __device__ __forceinline__ void outbox_tile(const OBArgs &a, uint64_t t, uint64_
   const auto [g0, n, o8, live, gid] = tile_at(a.G, a.goff, t, lane);
   const uint32_t sz = a.wide ? 2u : 1u, full = (1u << a.S) - 1u;
   // ---- 1. the masks: who sends what ----
-  const uint32_t ms = ob_ld_mask(ob_mask_rsrc(a.sent, g0, n, sz), lane, a.wide) & full;
-  const uint32_t mp = ob_ld_mask(ob_mask_rsrc(a.snap, g0, n, sz), lane, a.wide) & full;
-  const uint32_t mb = ob_ld_mask(ob_mask_rsrc(a.hb_sent, g0, n, sz), lane, a.wide) & full;
+  const uint32_t ms = list_ld_mask(list_mask_rsrc(a.sent, g0, n, sz), lane, a.wide) & full;
+  const uint32_t mp = list_ld_mask(list_mask_rsrc(a.snap, g0, n, sz), lane, a.wide) & full;
+  const uint32_t mb = list_ld_mask(list_mask_rsrc(a.hb_sent, g0, n, sz), lane, a.wide) & full;
   const uint32_t ma = ms & ~mp, mh = mb & ~(ms | mp);  // MsgSnap, then MsgApp, then MsgHeartbeat
   const uint32_t m = ma | mp | mh;
   const bool has = live && m != 0;
@@ -205,8 +163,7 @@ __device__ __forceinline__ void outbox_tile(const OBArgs &a, uint64_t t, uint64_
   }
   // ---- 4. the records, slot by slot ----
   // what of the arrays this tile may write: capacity is the descriptors'
-  const uint64_t tbc = tb < a.cap ? tb : a.cap;
-  const uint32_t rem = static_cast<uint32_t>(a.cap - tbc < kObTileMax ? a.cap - tbc : kObTileMax);
+  const auto [tbc, rem] = list_room(tb, a.cap, kObTileMax);
   const rsrc_t d_group = mk_rsrc(a.o_group + tbc, rem * 8), d_to = mk_rsrc(a.o_to + tbc, rem),
                d_type = mk_rsrc(a.o_type + tbc, rem), d_term = mk_rsrc(a.o_term + tbc, rem * 8),
                d_index = mk_rsrc(a.o_index + tbc, rem * 8),
@@ -228,6 +185,11 @@ __device__ __forceinline__ void outbox_tile(const OBArgs &a, uint64_t t, uint64_
     const bool bad = is_a && (nr == 0 || i < rf[0] || i > li);
     const bool app = is_a && !bad;
     const uint64_t hi = li - i > lim ? i + lim : li;
+    // run_cut of qe_step.hpp, written out: as a call, in any of the forms tried
+    // (arrays by reference, a struct by value, forced or left to the inliner), it
+    // costs every fill with entry runs 12-27 VGPRs at log_runs <= 8, with two
+    // waves per SIMD before and after; whether that costs time was not settled
+    // (DESIGN.md §6), so the registers decided
     uint32_t el[E > 0 ? E : 1] = {};
     uint64_t et[E > 0 ? E : 1] = {};
     uint32_t j = 0, ents = 0;
@@ -290,42 +252,13 @@ __device__ __forceinline__ void outbox_tile(const OBArgs &a, uint64_t t, uint64_
   cnt[O_GROUPS] += has ? 1u : 0u;
 }
 
-// A block per chunk (the blocks walk when the grid is capped for the
-// statistics): the chunk's tile counts, their exclusive scan in every wave, then
-// wave w fills the tiles 4k + w.
 template <int RM, int E>
 __global__ __launch_bounds__(kBlock) void k_outbox_fill(OBArgs a) {
-  __shared__ uint32_t tcnt[kObTiles];
-  uint64_t cnt[O_N] = {0, 0, 0, 0, 0, 0, 0, 0};
-  const uint32_t lane = threadIdx.x & 63;
-  const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  for (uint64_t c = blockIdx.x; c < a.nb; c += gridDim.x) {
-    chunk_tile_counts(a, a.wide != 0, c, tcnt);
-    __syncthreads();
-    const uint32_t x = tcnt[lane];
-    __syncthreads();  // (the next chunk's counts overwrite tcnt)
-    uint32_t inc = x;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t o = __shfl_up(inc, d, 64);
-      if (lane >= static_cast<uint32_t>(d)) inc += o;
-    }
-    const uint32_t pre = inc - x;
-    const uint64_t cbase = a.offsets[c];
-    for (uint32_t k = 0; k < kObRounds; k++) {
-      const uint32_t T = k * (kBlock / 64) + w;
-      if (__builtin_amdgcn_readfirstlane(__shfl(x, T, 64)) == 0) continue;  // no record
-      const uint64_t tb = cbase + __builtin_amdgcn_readfirstlane(__shfl(pre, T, 64));
-      outbox_tile<RM, E>(a, c * kObTiles + T, tb, lane, cnt);
-    }
-  }
-  if (a.stats) {
-    const int idx[O_N] = {QE_STAT_GROUPS,         QE_STAT_OUTBOX_APP,
-                          QE_STAT_OUTBOX_SNAP,    QE_STAT_OUTBOX_HEARTBEAT,
-                          QE_STAT_OUTBOX_BAD,     QE_STAT_INVARIANT_VIOLATIONS,
-                          QE_STAT_OUTBOX_ENTRIES, QE_STAT_CHECKSUM};
-    wave_stats_add<O_N>(cnt, idx, a.stats);
-  }
+  const int idx[O_N] = {QE_STAT_GROUPS,         QE_STAT_OUTBOX_APP,
+                        QE_STAT_OUTBOX_SNAP,    QE_STAT_OUTBOX_HEARTBEAT,
+                        QE_STAT_OUTBOX_BAD,     QE_STAT_INVARIANT_VIOLATIONS,
+                        QE_STAT_OUTBOX_ENTRIES, QE_STAT_CHECKSUM};
+  list_fill_walk<outbox_tile<RM, E>>(a, idx, OutboxCounts{a, a.wide != 0});
 }
 
 }  // namespace qe

@@ -8,7 +8,7 @@
 // applied and a pending snapshot.  Everything that takes is resident: term,
 // vote, lead, state, the log rows, and the eight rows of qe_ready_state.
 //
-// qe_ready is qe_outbox's three passes on qe_outbox's machinery:
+// qe_ready is the three passes of the record-list layer (qe_list.hpp):
 //   count   k_ready_count: one wave per 4096-group chunk.  Lane l of round j
 //           takes the groups 2 (64 j + l) and + 1 of the chunk: one 16-B load
 //           per u64 row and one 2-B load per byte row, each instruction a
@@ -17,11 +17,9 @@
 //           ragged last chunk, or rows that are not 16-B / 2-B aligned, take a
 //           lane per group.
 //   scan    k_collect_scan (qe_collect.hpp, launched by qe_ready);
-//   fill    k_ready_fill: k_outbox_fill's walk over the flag bytes
-//           (chunk_tile_counts reads them as a one-slot mask); a tile loads the
-//           rows of its listed groups only and writes one record per group, in
-//           lane order: a wave's stores are one contiguous run.  No block
-//           waits for another.
+//   fill    k_ready_fill: the layer's walk, its counts the flag bytes; a tile
+//           loads the rows of its listed groups only and writes one record
+//           per group, in lane order.
 // The fill reads the flag byte instead of recomputing the predicate: it costs
 // 2 B per group against the 87 B the predicate reads, and at the densities a
 // host sees (few groups have a Ready) the fill then touches almost nothing.
@@ -30,7 +28,7 @@
 // thread per record.  The kernels that are no templates (k_ready_count,
 // k_ready_note, k_advance) are defined in qe_inst_ready.hip.
 #pragma once
-#include "qe_outbox.hpp"
+#include "qe_list.hpp"
 
 namespace qe {
 
@@ -128,42 +126,6 @@ __device__ __forceinline__ uint32_t rd_flags(uint32_t S, uint64_t term, uint32_t
 
 enum { RD_RECORDS, RD_ENTRIES, RD_APPLY, RD_SYNC, RD_CSUM, RD_N };
 
-// (i, hi] cut into the table's runs (the last run ends at li), at most E of
-// them: qe_outbox rule 4.  -> the entries listed; `last` the term of the last
-// listed run.
-template <int RM, int E>
-__device__ __forceinline__ uint64_t rd_cut(const uint64_t (&rf)[RM], const uint64_t (&rt)[RM],
-                                           uint32_t nr, uint64_t li, uint64_t i, uint64_t hi,
-                                           bool on, uint32_t (&el)[E], uint64_t (&et)[E],
-                                           uint64_t &last) {
-  uint32_t j = 0;
-  uint64_t ents = 0;
-#pragma unroll
-  for (int k = 0; k < E; k++) {
-    el[k] = 0;
-    et[k] = 0;
-  }
-  last = 0;
-#pragma unroll
-  for (int r = 0; r < RM; r++) {
-    const uint64_t end = (r + 1 < RM && static_cast<uint32_t>(r + 1) < nr) ? rf[r + 1] - 1 : li;
-    const uint64_t lo = rf[r] > i ? rf[r] : i + 1, e = end < hi ? end : hi;
-    const bool ne = on && static_cast<uint32_t>(r) < nr && i < hi && lo <= e;
-    const uint32_t len = static_cast<uint32_t>(e) - static_cast<uint32_t>(lo) + 1u;
-    const bool in = ne && j < static_cast<uint32_t>(E);
-#pragma unroll
-    for (int k = 0; k < E; k++) {
-      const bool sel = ne && j == static_cast<uint32_t>(k);
-      el[k] = sel ? len : el[k];
-      et[k] = sel ? rt[r] : et[k];
-    }
-    ents += in ? len : 0u;
-    last = in ? rt[r] : last;
-    j += ne ? 1u : 0u;
-  }
-  return ents;
-}
-
 // Tile t, whose first record has position tb.
 template <int RM, int E>
 __device__ __forceinline__ void ready_tile(const RDArgs &a, uint64_t t, uint64_t tb, uint32_t lane,
@@ -211,12 +173,13 @@ __device__ __forceinline__ void ready_tile(const RDArgs &a, uint64_t t, uint64_t
   const uint64_t want = commit + 1 - off;
   const uint64_t ahi = (a.max_apply && want > a.max_apply) ? off + a.max_apply - 1 : commit;
   uint64_t ent_count, ent_last, apply_count;
-  uint32_t el[E > 0 ? E : 1], al[E > 0 ? E : 1];
-  uint64_t et[E > 0 ? E : 1], at[E > 0 ? E : 1];
+  RunCut<(E > 0 ? E : 1)> ec, ac;
   if constexpr (E > 0) {
-    uint64_t alast;
-    ent_count = rd_cut<RM, E>(rf, rt, nr, li, stable, li, ents, el, et, ent_last);
-    apply_count = rd_cut<RM, E>(rf, rt, nr, li, off - 1, ahi, apply, al, at, alast);
+    ec = run_cut<RM, E>(rf, rt, nr, li, stable, li, ents);
+    ac = run_cut<RM, E>(rf, rt, nr, li, off - 1, ahi, apply);
+    ent_count = ec.ents;
+    ent_last = ec.last;
+    apply_count = ac.ents;
   } else {
     ent_count = ents ? li - stable : 0;
     ent_last = ents ? run_term_at<RM>(rf, rt, nr, li, li) : 0;
@@ -229,8 +192,7 @@ __device__ __forceinline__ void ready_tile(const RDArgs &a, uint64_t t, uint64_t
   // ---- 4. the stores: the records of the tile in lane order ----
   const uint64_t bal = __builtin_amdgcn_ballot_w64(has);
   const uint32_t pos = lane_rank(bal);
-  const uint64_t tbc = tb < a.cap ? tb : a.cap;
-  const uint32_t rem = static_cast<uint32_t>(a.cap - tbc < 64 ? a.cap - tbc : 64);
+  const auto [tbc, rem] = list_room(tb, a.cap, 64);
   const uint32_t p1 = has ? pos : kOOB, p4 = has ? pos * 4 : kOOB, p8 = has ? pos * 8 : kOOB;
   bst64<kNT>(gid, mk_rsrc(a.o_group + tbc, rem * 8), p8);
   bst64<kNT>(term, mk_rsrc(a.o_term + tbc, rem * 8), p8);
@@ -249,10 +211,10 @@ __device__ __forceinline__ void ready_tile(const RDArgs &a, uint64_t t, uint64_t
 #pragma unroll
     for (int k = 0; k < E; k++) {
       const uint64_t row = static_cast<uint64_t>(k) * a.cap + tbc;
-      bst32<kNT>(el[k], mk_rsrc(a.o_ent_len + row, rem * 4), p4);
-      bst64<kNT>(et[k], mk_rsrc(a.o_ent_term + row, rem * 8), p8);
-      bst32<kNT>(al[k], mk_rsrc(a.o_apply_len + row, rem * 4), p4);
-      bst64<kNT>(at[k], mk_rsrc(a.o_apply_term + row, rem * 8), p8);
+      bst32<kNT>(ec.len[k], mk_rsrc(a.o_ent_len + row, rem * 4), p4);
+      bst64<kNT>(ec.term[k], mk_rsrc(a.o_ent_term + row, rem * 8), p8);
+      bst32<kNT>(ac.len[k], mk_rsrc(a.o_apply_len + row, rem * 4), p4);
+      bst64<kNT>(ac.term[k], mk_rsrc(a.o_apply_term + row, rem * 8), p8);
     }
   }
   if (a.stats) {
@@ -275,42 +237,22 @@ __device__ __forceinline__ void ready_tile(const RDArgs &a, uint64_t t, uint64_t
   }
 }
 
-// k_outbox_fill's walk with the flag bytes as the masks of one slot.
+// The counts of the layer: the flag bytes k_ready_count left.
+struct ReadyCounts {
+  const uint8_t *flag;
+  __device__ __forceinline__ void operator()(uint64_t base, uint32_t nc,
+                                             uint32_t (&k)[kListRounds]) const {
+    const rsrc_t rf = mk_rsrc(flag + base, nc);
+#pragma unroll
+    for (uint32_t r = 0; r < kListRounds; r++) k[r] = bld8<kNT>(rf, list_elem(r)) != 0 ? 1u : 0u;
+  }
+};
+
 template <int RM, int E>
 __global__ __launch_bounds__(kBlock) void k_ready_fill(RDArgs a) {
-  __shared__ uint32_t tcnt[kObTiles];
-  uint64_t cnt[RD_N] = {0, 0, 0, 0, 0};
-  const uint32_t lane = threadIdx.x & 63;
-  const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  OBArgs m{};
-  m.G = a.G;
-  m.S = 1;
-  m.sent = a.flag;
-  for (uint64_t c = blockIdx.x; c < a.nb; c += gridDim.x) {
-    chunk_tile_counts(m, false, c, tcnt);
-    __syncthreads();
-    const uint32_t x = tcnt[lane];
-    __syncthreads();  // (the next chunk's counts overwrite tcnt)
-    uint32_t inc = x;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t o = __shfl_up(inc, d, 64);
-      if (lane >= static_cast<uint32_t>(d)) inc += o;
-    }
-    const uint32_t pre = inc - x;
-    const uint64_t cbase = a.offsets[c];
-    for (uint32_t k = 0; k < kObRounds; k++) {
-      const uint32_t T = k * (kBlock / 64) + w;
-      if (__builtin_amdgcn_readfirstlane(__shfl(x, T, 64)) == 0) continue;  // no record
-      const uint64_t tb = cbase + __builtin_amdgcn_readfirstlane(__shfl(pre, T, 64));
-      ready_tile<RM, E>(a, c * kObTiles + T, tb, lane, cnt);
-    }
-  }
-  if (a.stats) {
-    const int idx[RD_N] = {QE_STAT_GROUPS, QE_STAT_READY_ENTRIES, QE_STAT_READY_APPLY,
-                           QE_STAT_READY_MUST_SYNC, QE_STAT_CHECKSUM};
-    wave_stats_add<RD_N>(cnt, idx, a.stats);
-  }
+  const int idx[RD_N] = {QE_STAT_GROUPS, QE_STAT_READY_ENTRIES, QE_STAT_READY_APPLY,
+                         QE_STAT_READY_MUST_SYNC, QE_STAT_CHECKSUM};
+  list_fill_walk<ready_tile<RM, E>>(a, idx, ReadyCounts{a.flag});
 }
 
 }  // namespace qe

@@ -10,22 +10,17 @@
 // MsgTimeoutNow of qe_progress_step (sendTimeoutNow, :1722-1724).  Everything a
 // record needs is in those rows and the sender's term.
 //
-// qe_outbox's three passes on qe_outbox's machinery (chunks, lane_rank, the
-// mask descriptors): k_replies_count, k_collect_scan (qe_collect.hpp),
-// k_replies_fill; no block waits for another.  The count reads only bytes: the
-// three result rows, v_req_to under the ballot of the lanes that campaign, and
-// timeout_now where it is given.  A tile in the house idiom (qe_step.hpp): one
-// lane per group; the results, then the rows of each kind under the ballot of
-// the lanes that need them, then the records kind by kind (F, S, V response, V
-// request slot by slot, T slot by slot).  The records of a (kind[, slot]) take
-// consecutive positions in lane order, so a wave's stores for one are one
-// contiguous run.  Every store follows every load of the tile.  Capacity is the
-// output descriptors' num_records.  Every access is non-temporal.
+// The three passes of the record-list layer (qe_list.hpp): k_replies_count and
+// k_replies_fill.  The counts read only bytes: the three result rows, v_req_to
+// under the ballot of the lanes that campaign, and timeout_now where it is
+// given.  A tile: one lane per group; the results, then the rows of each kind
+// under the ballot of the lanes that need them, then the records kind by kind
+// (F, S, V response, V request slot by slot, T slot by slot).
 //
 // The slot count and the mask width are run-time values and there is no run
 // table: one object.
 #pragma once
-#include "qe_outbox.hpp"
+#include "qe_list.hpp"
 
 namespace qe {
 
@@ -80,58 +75,43 @@ __device__ __forceinline__ bool rp_f_sends(uint32_t r) { return r - 2u <= 4u; }
 __device__ __forceinline__ bool rp_s_sends(uint32_t r) { return r - 2u <= 3u; }
 __device__ __forceinline__ bool rp_v_responds(uint32_t r) { return r - 3u <= 1u; }
 __device__ __forceinline__ bool rp_campaigns(uint32_t r) { return r - 8u <= 1u; }
-// element i of a mask row for the lanes with `on`
-__device__ __forceinline__ uint32_t rp_ld_mask(rsrc_t r, uint32_t i, bool wide, bool on) {
-  return wide ? bld16<kNT>(r, on ? i * 2 : kOOB) : bld8<kNT>(r, on ? i : kOOB);
-}
 
-// chunk_tile_counts of qe_outbox.hpp for the replies: the results and
-// timeout_now of all rounds in flight together, then v_req_to round by round
-// under the ballot of the campaigns.
-__device__ __forceinline__ void replies_tile_counts(const RPArgs &a, bool wide, uint64_t c,
-                                                    uint32_t *tcnt) {
-  const uint32_t tid = threadIdx.x, lane = tid & 63;
-  const uint32_t w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const uint64_t base = c * kObChunk;
-  const uint32_t nc = static_cast<uint32_t>(a.G - base < kObChunk ? a.G - base : kObChunk);
-  const uint32_t sz = wide ? 2u : 1u, full = (1u << a.S) - 1u;
-  const rsrc_t rf = opt_rsrc(a.f_result, base, nc), rs = opt_rsrc(a.s_result, base, nc),
-               rv = opt_rsrc(a.v_result, base, nc);
-  const rsrc_t rq = ob_mask_rsrc(a.v_req_to, base, nc, sz),
-               rt = ob_mask_rsrc(a.timeout_now, base, nc, sz);
-  uint32_t k[kObRounds], vr[kObRounds];
+// The counts of the layer: the results and timeout_now of all rounds in flight
+// together, then v_req_to round by round under the ballot of the campaigns.
+// `wide`: the masks are 16-bit words.
+struct RepliesCounts {
+  const RPArgs &a;
+  bool wide;
+  __device__ __forceinline__ void operator()(uint64_t base, uint32_t nc,
+                                             uint32_t (&k)[kListRounds]) const {
+    const uint32_t sz = wide ? 2u : 1u, full = (1u << a.S) - 1u;
+    const rsrc_t rf = opt_rsrc(a.f_result, base, nc), rs = opt_rsrc(a.s_result, base, nc),
+                 rv = opt_rsrc(a.v_result, base, nc);
+    const rsrc_t rq = list_mask_rsrc(a.v_req_to, base, nc, sz),
+                 rt = list_mask_rsrc(a.timeout_now, base, nc, sz);
+    uint32_t vr[kListRounds];
 #pragma unroll
-  for (uint32_t r = 0; r < kObRounds; r++) {
-    const uint32_t i = r * kBlock + tid;  // past nc: out of range, reads 0
-    const uint32_t fr = bld8<kNT>(rf, i), sr = bld8<kNT>(rs, i);
-    vr[r] = bld8<kNT>(rv, i);
-    const uint32_t mt = ob_ld_mask(rt, i, wide) & full;
-    k[r] = (rp_f_sends(fr) ? 1u : 0u) + (rp_s_sends(sr) ? 1u : 0u) +
-           (rp_v_responds(vr[r]) ? 1u : 0u) + popc(mt);
-  }
+    for (uint32_t r = 0; r < kListRounds; r++) {
+      const uint32_t i = list_elem(r);
+      const uint32_t fr = bld8<kNT>(rf, i), sr = bld8<kNT>(rs, i);
+      vr[r] = bld8<kNT>(rv, i);
+      const uint32_t mt = list_ld_mask(rt, i, wide) & full;
+      k[r] = (rp_f_sends(fr) ? 1u : 0u) + (rp_s_sends(sr) ? 1u : 0u) +
+             (rp_v_responds(vr[r]) ? 1u : 0u) + popc(mt);
+    }
 #pragma unroll
-  for (uint32_t r = 0; r < kObRounds; r++) {
-    const bool camp = rp_campaigns(vr[r]);
-    if (__builtin_amdgcn_ballot_w64(camp))
-      k[r] += popc(rp_ld_mask(rq, r * kBlock + tid, wide, camp) & full);
+    for (uint32_t r = 0; r < kListRounds; r++) {
+      const bool camp = rp_campaigns(vr[r]);
+      if (__builtin_amdgcn_ballot_w64(camp))
+        k[r] += popc(list_ld_mask(rq, list_elem(r), wide, camp) & full);
+    }
   }
-#pragma unroll
-  for (uint32_t r = 0; r < kObRounds; r++) {
-    const uint32_t s = wave_sum_u32(k[r]);
-    if (lane == 0) tcnt[r * (kBlock / 64) + w] = s;
-  }
-}
+};
 
-// One block per chunk.  WIDE: the masks are 16-bit words.
+// WIDE: the masks are 16-bit words.
 template <bool WIDE>
 __global__ __launch_bounds__(kBlock) void k_replies_count(RPArgs a) {
-  __shared__ uint32_t tcnt[kObTiles];
-  replies_tile_counts(a, WIDE, blockIdx.x, tcnt);
-  __syncthreads();
-  if (threadIdx.x < 64) {
-    const uint32_t s = wave_sum_u32(tcnt[threadIdx.x]);
-    if (threadIdx.x == 0) a.counts[blockIdx.x] = s;
-  }
+  list_count_block(a.G, a.counts, RepliesCounts{a, WIDE});
 }
 
 enum { RP_GROUPS, RP_APP, RP_HB, RP_VRESP, RP_VREQ, RP_TN, RP_BAD, RP_VIOL, RP_CSUM, RP_N };
@@ -174,8 +154,10 @@ __device__ __forceinline__ uint32_t rp_emit(const RPOut &d, bool stats, bool bit
 }
 
 // Tile t, whose first record has position tb.
-__device__ __forceinline__ void replies_tile(const RPArgs &a, bool wide, uint64_t t, uint64_t tb,
+template <bool WIDE>
+__device__ __forceinline__ void replies_tile(const RPArgs &a, uint64_t t, uint64_t tb,
                                              uint32_t lane, uint64_t (&cnt)[RP_N]) {
+  constexpr bool wide = WIDE;
   const auto [g0, n, o8, live, gid] = tile_at(a.G, a.goff, t, lane);
   const bool stats = a.stats != nullptr;
   const uint32_t sz = wide ? 2u : 1u, S = a.S, full = (1u << S) - 1u;
@@ -183,12 +165,12 @@ __device__ __forceinline__ void replies_tile(const RPArgs &a, bool wide, uint64_
   const uint32_t fr = bld8<kNT>(opt_rsrc(a.f_result, g0, n), lane);
   const uint32_t sr = bld8<kNT>(opt_rsrc(a.s_result, g0, n), lane);
   const uint32_t vr = bld8<kNT>(opt_rsrc(a.v_result, g0, n), lane);
-  const uint32_t mt = ob_ld_mask(ob_mask_rsrc(a.timeout_now, g0, n, sz), lane, wide) & full;
+  const uint32_t mt = list_ld_mask(list_mask_rsrc(a.timeout_now, g0, n, sz), lane, wide) & full;
   const bool is_f = rp_f_sends(fr), is_s = rp_s_sends(sr), is_v = rp_v_responds(vr),
              camp = rp_campaigns(vr);
   uint32_t mq = 0;
   if (__builtin_amdgcn_ballot_w64(camp))
-    mq = rp_ld_mask(ob_mask_rsrc(a.v_req_to, g0, n, sz), lane, wide, camp) & full;
+    mq = list_ld_mask(list_mask_rsrc(a.v_req_to, g0, n, sz), lane, wide, camp) & full;
   // ---- 2. the rows of each kind, under the ballot of the lanes that need them ----
   const bool need_t = is_f || is_s || mt != 0;
   uint64_t term = 0;
@@ -229,8 +211,7 @@ __device__ __forceinline__ void replies_tile(const RPArgs &a, bool wide, uint64_
   }
   // ---- 3. the records, kind by kind ----
   // what of the arrays this tile may write: capacity is the descriptors'
-  const uint64_t tbc = tb < a.cap ? tb : a.cap;
-  const uint32_t rem = static_cast<uint32_t>(a.cap - tbc < kRpTileMax ? a.cap - tbc : kRpTileMax);
+  const auto [tbc, rem] = list_room(tb, a.cap, kRpTileMax);
   const RPOut d = {mk_rsrc(a.o_group + tbc, rem * 8),
                    mk_rsrc(a.o_to + tbc, rem),
                    mk_rsrc(a.o_type + tbc, rem),
@@ -306,43 +287,15 @@ __device__ __forceinline__ void replies_tile(const RPArgs &a, bool wide, uint64_
   cnt[RP_GROUPS] += (is_f || is_s || is_v || mq != 0 || mt != 0) ? 1u : 0u;
 }
 
-// k_outbox_fill's walk: a block per chunk (the blocks walk when the grid is
-// capped for the statistics), the chunk's tile counts, their exclusive scan in
-// every wave, then wave w fills the tiles 4k + w.  WIDE as k_replies_count's.
+// WIDE as k_replies_count's.
 template <bool WIDE>
 __global__ __launch_bounds__(kBlock) void k_replies_fill(RPArgs a) {
-  __shared__ uint32_t tcnt[kObTiles];
-  uint64_t cnt[RP_N] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  const uint32_t lane = threadIdx.x & 63;
-  const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  for (uint64_t c = blockIdx.x; c < a.nb; c += gridDim.x) {
-    replies_tile_counts(a, WIDE, c, tcnt);
-    __syncthreads();
-    const uint32_t x = tcnt[lane];
-    __syncthreads();  // (the next chunk's counts overwrite tcnt)
-    uint32_t inc = x;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t o = __shfl_up(inc, d, 64);
-      if (lane >= static_cast<uint32_t>(d)) inc += o;
-    }
-    const uint32_t pre = inc - x;
-    const uint64_t cbase = a.offsets[c];
-    for (uint32_t k = 0; k < kObRounds; k++) {
-      const uint32_t T = k * (kBlock / 64) + w;
-      if (__builtin_amdgcn_readfirstlane(__shfl(x, T, 64)) == 0) continue;  // no record
-      const uint64_t tb = cbase + __builtin_amdgcn_readfirstlane(__shfl(pre, T, 64));
-      replies_tile(a, WIDE, c * kObTiles + T, tb, lane, cnt);
-    }
-  }
-  if (a.stats) {
-    const int idx[RP_N] = {QE_STAT_GROUPS,          QE_STAT_REPLY_APP_RESP,
-                          QE_STAT_REPLY_HEARTBEAT_RESP, QE_STAT_REPLY_VOTE_RESP,
-                          QE_STAT_REPLY_VOTE_REQ,  QE_STAT_REPLY_TIMEOUT_NOW,
-                          QE_STAT_REPLY_BAD,       QE_STAT_INVARIANT_VIOLATIONS,
-                          QE_STAT_CHECKSUM};
-    wave_stats_add<RP_N>(cnt, idx, a.stats);
-  }
+  const int idx[RP_N] = {QE_STAT_GROUPS,          QE_STAT_REPLY_APP_RESP,
+                         QE_STAT_REPLY_HEARTBEAT_RESP, QE_STAT_REPLY_VOTE_RESP,
+                         QE_STAT_REPLY_VOTE_REQ,  QE_STAT_REPLY_TIMEOUT_NOW,
+                         QE_STAT_REPLY_BAD,       QE_STAT_INVARIANT_VIOLATIONS,
+                         QE_STAT_CHECKSUM};
+  list_fill_walk<replies_tile<WIDE>>(a, idx, RepliesCounts{a, WIDE});
 }
 
 }  // namespace qe

@@ -1,8 +1,9 @@
 // qe_step.hpp — what the receiver-side step kernels share (k_tick, k_follow,
 // k_vote, k_snap, k_compact; each in a header of its own on this one): the
 // tile prologue, the header part of becomeFollower(m.Term, from) for a
-// message from a leader, raftLog.term over a term-run table in registers,
-// and the result / events rows every tile ends with.
+// message from a leader, raftLog.term over a term-run table in registers, the
+// cut of an entry range into the table's runs (qe_ready's lists), and the
+// result / events rows every tile ends with.
 //
 // Two more pieces are the same text in two kernels and stay written out
 // there: the term preamble (lower / higher / lead_same / proceed / bf, k_follow
@@ -78,6 +79,43 @@ __device__ __forceinline__ uint64_t run_term_at(const uint64_t (&rf)[RM], const 
 #pragma unroll
   for (int r = 0; r < RM; r++) t = (static_cast<uint32_t>(r) < nr && i >= rf[r]) ? rt[r] : t;
   return (nr == 0 || i < rf[0] || i > li) ? 0 : t;
+}
+
+// The entries (i, hi] cut into the table's runs (the last run ends at li), at
+// most E of them, for the lanes with `on`: qe_outbox rule 4.  -> len / term:
+// the length and the term of each listed run, 0 past the last; the entries
+// listed; the term of the last listed run.  (qe_ready's two lists; outbox_tile
+// holds the same cut written out, see there.)
+template <int E>
+struct RunCut {
+  uint32_t len[E];
+  uint64_t term[E];
+  uint64_t ents, last;
+};
+template <int RM, int E>
+__device__ __forceinline__ RunCut<E> run_cut(const uint64_t (&rf)[RM], const uint64_t (&rt)[RM],
+                                             uint32_t nr, uint64_t li, uint64_t i, uint64_t hi,
+                                             bool on) {
+  uint32_t j = 0;
+  RunCut<E> c = {};
+#pragma unroll
+  for (int r = 0; r < RM; r++) {
+    const uint64_t end = (r + 1 < RM && static_cast<uint32_t>(r + 1) < nr) ? rf[r + 1] - 1 : li;
+    const uint64_t lo = rf[r] > i ? rf[r] : i + 1, e = end < hi ? end : hi;
+    const bool ne = on && static_cast<uint32_t>(r) < nr && i < hi && lo <= e;
+    const uint32_t len = static_cast<uint32_t>(e) - static_cast<uint32_t>(lo) + 1u;
+    const bool in = ne && j < static_cast<uint32_t>(E);
+#pragma unroll
+    for (int k = 0; k < E; k++) {
+      const bool sel = ne && j == static_cast<uint32_t>(k);
+      c.len[k] = sel ? len : c.len[k];
+      c.term[k] = sel ? rt[r] : c.term[k];
+    }
+    c.ents += in ? len : 0u;
+    c.last = in ? rt[r] : c.last;
+    j += ne ? 1u : 0u;
+  }
+  return c;
 }
 
 // What every tile ends with: the result of every group, and its QE_TEV_*

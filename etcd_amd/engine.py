@@ -802,7 +802,7 @@ class _Rows:
     def __init_subclass__(cls):
         words = [w.rstrip("?").split(":") for w in cls.FIELDS.split()]
         cls.ARRAYS, cls.KIND = tuple(w[0] for w in words), dict(words)
-        cls.HOST = getattr(cls, "HOST", cls.ARRAYS)
+        cls.HOST = cls.__dict__.get("HOST", cls.ARRAYS)  # (a base's HOST is its own)
 
     def load_host(self, **arrays):
         for k, a in arrays.items():
@@ -827,6 +827,46 @@ class _Rows:
                 a = a.view(kind or (np.uint8 if a.dtype == np.uint8 else np.uint16))
             out[k] = a
         return out
+
+
+_TORCH = {"u8": torch.uint8, "u32": torch.int32, "u64": torch.int64}
+
+
+class _Records(_Rows):
+    """What the record lists of qe_outbox, qe_replies and qe_ready share: rows
+    of max(1, capacity) records allocated from FIELDS, the rows named in RUNS
+    as [E][capacity] term runs (left out with E = 0), `count` (int64[1]), the
+    cached scratch of the call, and records()."""
+
+    RUNS = ()
+
+    def _alloc(self, device, capacity, runs=0, without=()):
+        self.capacity = int(capacity)
+        n = max(1, self.capacity)
+        for k in self.ARRAYS:
+            size = 1 if k == "count" else runs * n if k in self.RUNS else n
+            setattr(self, k, None if k in without or not size else
+                    torch.zeros(size, dtype=_TORCH[self.KIND[k]], device=device))
+        self.scratch = None
+
+    def records(self):
+        """-> (count, the rows cut to min(count, capacity) as numpy arrays:
+        the run rows as [E][n], None for a row left out)."""
+        count = int(self.count.item())
+        n, cap = min(count, self.capacity), max(1, self.capacity)
+        out = {k: a for k, a in self.host().items() if k != "count"}
+        for k, a in out.items():
+            if a is not None:
+                out[k] = a.reshape(-1, cap)[:, :n] if k in self.RUNS else a[:n]
+        return count, out
+
+
+def _scratch(obj, device, need, grow=0):
+    """The scratch tensor cached in `obj` for a call that needs `need` bytes,
+    allocated with max(need, grow) bytes when there is none or it is too small."""
+    if obj.scratch is None or obj.scratch.numel() * 8 < need:
+        obj.scratch = torch.empty((max(need, grow) + 7) // 8 + 1, dtype=torch.int64, device=device)
+    return obj.scratch
 
 
 class Follower(_Rows):
@@ -1100,7 +1140,7 @@ def snapshot_step(ps, fol, conf, msgs, out=None, stats=None):
     return out
 
 
-class Outbox(_Rows):
+class Outbox(_Records):
     """The record arrays of qe_outbox (qe_outbox_out) for up to `capacity`
     messages: group / term / index / log_term / commit int64 storage of the u64
     fields, to / type u8 (QE_OMSG_*), ctx int32, the entries of a MsgApp as
@@ -1110,40 +1150,19 @@ class Outbox(_Rows):
 
     FIELDS = ("group:u64 to:u8 type:u8 term:u64 index:u64 log_term:u64 commit:u64 ctx:u32 "
               "ent_len:u32? ent_term:u64? count:u64")
+    RUNS = ("ent_len", "ent_term")
 
     def __init__(self, ps, capacity, msg_runs=_lib.QE_MAX_MSG_RUNS):
         if not 0 <= int(msg_runs) <= _lib.QE_MAX_MSG_RUNS:
             raise ValueError("msg_runs must be 0..QE_MAX_MSG_RUNS")
-        dev, i64, u8 = ps.device, torch.int64, torch.uint8
-        self.capacity, self.msg_runs = int(capacity), int(msg_runs)
-        n = max(1, self.capacity)
-        for k in ("group", "term", "index", "log_term", "commit"):
-            setattr(self, k, torch.zeros(n, dtype=i64, device=dev))
-        self.to = torch.zeros(n, dtype=u8, device=dev)
-        self.type = torch.zeros(n, dtype=u8, device=dev)
-        self.ctx = torch.zeros(n, dtype=torch.int32, device=dev)
-        e = self.msg_runs * n
-        self.ent_len = torch.zeros(e, dtype=torch.int32, device=dev) if e else None
-        self.ent_term = torch.zeros(e, dtype=i64, device=dev) if e else None
-        self.count = torch.zeros(1, dtype=i64, device=dev)
-        self.scratch = None
+        self.msg_runs = int(msg_runs)
+        self._alloc(ps.device, capacity, self.msg_runs)
 
     def struct(self):
         return _lib.QeOutboxOut(self.capacity, self.msg_runs, 0, _ptr(self.group), _ptr(self.to),
                                 _ptr(self.type), _ptr(self.term), _ptr(self.index),
                                 _ptr(self.log_term), _ptr(self.commit), _ptr(self.ctx),
                                 _ptr(self.ent_len), _ptr(self.ent_term), _ptr(self.count))
-
-    def records(self):
-        """-> (count, the rows cut to min(count, capacity) as numpy arrays;
-        ent_len / ent_term as [E][n])."""
-        count = int(self.count.item())
-        n, cap = min(count, self.capacity), max(1, self.capacity)
-        h = self.host()
-        out = {k: h[k][:n] for k in self.ARRAYS if k not in ("ent_len", "ent_term", "count")}
-        for k in ("ent_len", "ent_term"):
-            out[k] = None if h[k] is None else h[k].reshape(self.msg_runs, cap)[:, :n]
-        return count, out
 
 
 def outbox(ps, term, ob, sent=None, snap=None, index=None, next_before=None, hb_sent=None,
@@ -1156,9 +1175,7 @@ def outbox(ps, term, ob, sent=None, snap=None, index=None, next_before=None, hb_
     report none, from `next_before` (a clone of ps.next taken before the call;
     ps.next itself after become_leader).  Nothing of `ps` is written."""
     lib = _lib.lib()
-    if ob.scratch is None:
-        ob.scratch = torch.empty((lib.qe_outbox_scratch_bytes(ps.G) + 7) // 8 + 1,
-                                 dtype=torch.int64, device=ps.device)
+    _scratch(ob, ps.device, lib.qe_outbox_scratch_bytes(ps.G))
     p, o = ps.struct(), ob.struct()
     i = _lib.QeOutboxIn(_ptr(sent), _ptr(snap), _ptr(hb_sent), _ptr(index), _ptr(next_before),
                         _ptr(term), _ptr(snap_term), _ptr(hb_commit), _ptr(hb_ctx),
@@ -1168,7 +1185,7 @@ def outbox(ps, term, ob, sent=None, snap=None, index=None, next_before=None, hb_
     return ob
 
 
-class Replies(_Rows):
+class Replies(_Records):
     """The record arrays of qe_replies (qe_replies_out) for up to `capacity`
     messages, in the layout an Inbox takes: group / term / index / log_term /
     hint int64 storage of the u64 fields, to / type u8 (QE_IMSG_* or
@@ -1180,28 +1197,11 @@ class Replies(_Rows):
               "flags:u8? count:u64")
 
     def __init__(self, ps, capacity, ctx=True, flags=True):
-        dev, i64, u8 = ps.device, torch.int64, torch.uint8
-        self.capacity = int(capacity)
-        n = max(1, self.capacity)
-        for k in ("group", "term", "index", "log_term", "hint"):
-            setattr(self, k, torch.zeros(n, dtype=i64, device=dev))
-        self.to = torch.zeros(n, dtype=u8, device=dev)
-        self.type = torch.zeros(n, dtype=u8, device=dev)
-        self.ctx = torch.zeros(n, dtype=torch.int32, device=dev) if ctx else None
-        self.flags = torch.zeros(n, dtype=u8, device=dev) if flags else None
-        self.count = torch.zeros(1, dtype=i64, device=dev)
-        self.scratch = None
+        self._alloc(ps.device, capacity,
+                    without=(() if ctx else ("ctx",)) + (() if flags else ("flags",)))
 
     def struct(self):
         return _lib.QeRepliesOut(self.capacity, *[_ptr(getattr(self, k)) for k in self.ARRAYS])
-
-    def records(self):
-        """-> (count, the rows cut to min(count, capacity) as numpy arrays,
-        None for a row left out)."""
-        count = int(self.count.item())
-        n = min(count, self.capacity)
-        h = self.host()
-        return count, {k: None if h[k] is None else h[k][:n] for k in self.ARRAYS if k != "count"}
 
 
 def replies(ps, term, rp, follow=None, snap=None, vote=None, timeout_now=None, f_ctx=None,
@@ -1214,9 +1214,7 @@ def replies(ps, term, rp, follow=None, snap=None, vote=None, timeout_now=None, f
     heartbeats carried.  `term` is the Follower's term row AFTER those calls.
     Nothing of `ps` is written."""
     lib = _lib.lib()
-    if rp.scratch is None:
-        rp.scratch = torch.empty((lib.qe_replies_scratch_bytes(ps.G) + 7) // 8 + 1,
-                                 dtype=torch.int64, device=ps.device)
+    _scratch(rp, ps.device, lib.qe_replies_scratch_bytes(ps.G))
     i = _lib.QeRepliesIn(term=_ptr(term), timeout_now=_ptr(timeout_now), f_ctx=_ptr(f_ctx))
     if follow is not None:
         m, o = follow
@@ -1274,7 +1272,7 @@ class ReadyState(_Rows):
         return _lib.QeReadyState(*[_ptr(getattr(self, k)) for k in self.ARRAYS])
 
 
-class Ready(_Rows):
+class Ready(_Records):
     """The record arrays of qe_ready (qe_ready_out) for up to `capacity`
     groups: group / term / commit / ent_first / ent_count / ent_last_term /
     apply_first / apply_count / snap_index int64 storage of the u64 fields,
@@ -1284,8 +1282,6 @@ class Ready(_Rows):
     groups listed, which may exceed capacity.  The scratch of the call and the
     result row of advance() are cached here."""
 
-    U64 = ("group", "term", "commit", "ent_first", "ent_count", "ent_last_term", "apply_first",
-           "apply_count", "snap_index")
     FIELDS = ("group:u64 term:u64 commit:u64 vote:u8 lead:u8 state:u8 flags:u8 ent_first:u64 "
               "ent_count:u64 ent_last_term:u64 apply_first:u64 apply_count:u64 snap_index:u64 "
               "ent_len:u32? ent_term:u64? apply_len:u32? apply_term:u64? count:u64")
@@ -1294,35 +1290,13 @@ class Ready(_Rows):
     def __init__(self, ps, capacity, ent_runs=_lib.QE_MAX_MSG_RUNS):
         if not 0 <= int(ent_runs) <= _lib.QE_MAX_MSG_RUNS:
             raise ValueError("ent_runs must be 0..QE_MAX_MSG_RUNS")
-        dev, i64, u8 = ps.device, torch.int64, torch.uint8
-        self.capacity, self.ent_runs = int(capacity), int(ent_runs)
-        n = max(1, self.capacity)
-        for k in self.U64:
-            setattr(self, k, torch.zeros(n, dtype=i64, device=dev))
-        for k in ("vote", "lead", "state", "flags"):
-            setattr(self, k, torch.zeros(n, dtype=u8, device=dev))
-        e = self.ent_runs * n
-        for k in self.RUNS:
-            dt = torch.int32 if k.endswith("len") else i64
-            setattr(self, k, torch.zeros(e, dtype=dt, device=dev) if e else None)
-        self.count = torch.zeros(1, dtype=i64, device=dev)
-        self.result = torch.zeros(n, dtype=u8, device=dev)
-        self.scratch = None
+        self.ent_runs = int(ent_runs)
+        self._alloc(ps.device, capacity, self.ent_runs)
+        self.result = torch.zeros_like(self.flags)
 
     def struct(self):
         return _lib.QeReadyOut(self.capacity, self.ent_runs, 0,
                                *[_ptr(getattr(self, k)) for k in self.ARRAYS])
-
-    def records(self):
-        """-> (count, the rows cut to min(count, capacity) as numpy arrays; the
-        run rows as [E][n], None with ent_runs 0)."""
-        count = int(self.count.item())
-        n, cap = min(count, self.capacity), max(1, self.capacity)
-        h = self.host()
-        out = {k: h[k][:n] for k in self.ARRAYS if k not in self.RUNS and k != "count"}
-        for k in self.RUNS:
-            out[k] = None if h[k] is None else h[k].reshape(self.ent_runs, cap)[:, :n]
-        return count, out
 
 
 def ready_note(ps, rs, follow=None, snap=None):
@@ -1346,9 +1320,7 @@ def ready(ps, fol, rs, rd, pending=None, max_apply=0, stats=None):
     ascending group.  `pending` [G] u8 marks groups to list whatever their
     state (messages, ReadStates).  Nothing resident is written."""
     lib = _lib.lib()
-    if rd.scratch is None:
-        rd.scratch = torch.empty((lib.qe_ready_scratch_bytes(ps.G) + 7) // 8 + 1,
-                                 dtype=torch.int64, device=ps.device)
+    _scratch(rd, ps.device, lib.qe_ready_scratch_bytes(ps.G))
     p, f, r, o = ps.struct(), fol.struct(), rs.struct(), rd.struct()
     i = _lib.QeReadyIn(_ptr(pending), int(max_apply), 0)
     check("qe_ready", lib.qe_ready(C.byref(p), C.byref(f), C.byref(r), C.byref(i), C.byref(o),
@@ -1491,11 +1463,8 @@ def inbox(ps, fol, ib, lm, sm, vm, pm, tick_action=None, stats=None):
     if lm.msg_runs != ib.msg_runs:
         raise ValueError("the LeaderMsgs and the Inbox differ in msg_runs")
     lib = _lib.lib()
-    need = lib.qe_inbox_scratch_bytes(ps.G, ps.S, ib.n)
-    if ib.scratch is None or ib.scratch.numel() * 8 < need:
-        grow = lib.qe_inbox_scratch_bytes(ps.G, ps.S, max(1, ib.capacity))
-        ib.scratch = torch.empty((max(need, grow) + 7) // 8 + 1, dtype=torch.int64,
-                                 device=ps.device)
+    _scratch(ib, ps.device, lib.qe_inbox_scratch_bytes(ps.G, ps.S, ib.n),
+             grow=lib.qe_inbox_scratch_bytes(ps.G, ps.S, max(1, ib.capacity)))
     p, f = ps.struct(), fol.struct()
     i = _lib.QeInboxIn(ib.n, ib.msg_runs, 0, _ptr(ib.group), _ptr(ib.from_), _ptr(ib.type),
                        _ptr(ib.term), _ptr(ib.index), _ptr(ib.log_term), _ptr(ib.commit),

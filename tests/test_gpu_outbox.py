@@ -20,7 +20,7 @@ from tests import outbox_model as om
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 SENT = 0x0E0E0E0E0E0E0E0E
-CHUNK = 4096  # kObChunk (etcd_amd/csrc/qe_outbox.hpp), checked in test_chunk_size
+CHUNK = 4096  # kListChunk (etcd_amd/csrc/qe_list.hpp), checked in test_chunk_size
 BIG = 3 * CHUNK + 65
 GOFF = 1 << 33
 NP = {torch.int64: np.uint64, torch.int32: np.uint32, torch.int16: np.uint16, torch.uint8: np.uint8}
@@ -227,3 +227,81 @@ def test_outbox_matches_model(eng, G, S, R, E, density, kinds, src, max_entries,
     # ---- the statistics count every record, past capacity too ----
     for i in range(16):
         assert int(folded[i]) == mstats.get(i, 0), ("stat", i)
+
+
+def walk_groups():
+    """The smallest batch at which a fill block takes a second chunk: with
+    statistics the fill grid is capped at 8 blocks per CU, so one chunk more
+    than that, and the ragged 65 groups of BIG."""
+    cus = torch.cuda.get_device_properties(DEV).multi_processor_count
+    return (8 * cus + 1) * CHUNK + 65
+
+
+class DeviceRandom:
+    """Seeded random rows of G groups, generated on the device."""
+
+    def __init__(self, G, seed):
+        self.G, self.gen = G, torch.Generator(device=DEV).manual_seed(seed)
+
+    def ints(self, lo, hi, dtype=torch.int64):
+        return torch.randint(lo, hi, (self.G,), generator=self.gen, device=DEV).to(dtype)
+
+    def hit(self, p):
+        """True for about p of the groups."""
+        return torch.rand(self.G, generator=self.gen, device=DEV) < p
+
+
+def same_list(a, b, runs, width):
+    """-> the common count of two record lists, after comparing count and
+    every record array up to it on the device; the rows named in `runs` are
+    [E][capacity]."""
+    assert torch.equal(a.count, b.count), "count"
+    n = int(a.count.item())
+    assert 0 < n <= a.capacity == b.capacity
+    for k in a.ARRAYS:
+        x, y = getattr(a, k), getattr(b, k)
+        if k == "count" or x is None:
+            assert k == "count" or y is None
+            continue
+        if k in runs:
+            x, y = x.view(width, -1)[:, :n], y.view(width, -1)[:, :n]
+        else:
+            x, y = x[:n], y[:n]
+        assert torch.equal(x, y), k
+    return n
+
+
+def test_fill_blocks_walk(eng):
+    """A batch of one chunk more than the capped fill grid has blocks: with
+    statistics a block takes a second chunk.  The list of that call against the
+    list of the call without statistics (a block per chunk, what the model
+    tests pin), and the counters the list alone determines."""
+    e, L = eng, eng._lib
+    G, S, R, E = walk_groups(), 1, 1, 1
+    rnd = DeviceRandom(G, 0x0B0C)
+    ps = e.ProgressState(G, S, 1, R, DEV, group_offset=GOFF, extras=("snap_index",))
+    ps.run_first[:G], ps.run_term[:G], ps.run_count[:] = 5, 3, 1
+    ps.last_index.copy_(5 + rnd.ints(0, 12))
+    ps.committed.fill_(5)
+    ps.snap_index.fill_(4)
+    index = torch.zeros(S * ps.stride, dtype=torch.int64, device=DEV)
+    index[:G] = 5 + rnd.ints(0, 13)  # a few past last_index: QE_OMSG_BAD
+    hb_commit = torch.zeros(S * ps.stride, dtype=torch.int64, device=DEV)
+    hb_commit[:G] = rnd.ints(0, 1 << 40)
+    sent, snap, hb = (rnd.hit(p).to(torch.uint8) for p in (0.01, 0.003, 0.01))
+    term, ctx = rnd.ints(1, 1 << 40), rnd.ints(0, 1 << 31, torch.int32)
+    cap = int(((sent | snap | hb) & 1).sum().item()) + 5  # one slot: a record per group at most
+    lists = []
+    for stats in (None, e.stats_buffer(DEV)):
+        ob = e.Outbox(ps, cap, E)
+        e.outbox(ps, term, ob, sent=sent, snap=snap, index=index, hb_sent=hb, hb_commit=hb_commit,
+                 hb_ctx=ctx, stats=stats)
+        lists.append(ob)
+    n = same_list(lists[0], lists[1], ("ent_len", "ent_term"), E)
+    folded = e.stats_reduce(stats)
+    t = lists[0].type[:n]
+    per_type = {L.QE_STAT_OUTBOX_APP: L.QE_OMSG_APP, L.QE_STAT_OUTBOX_SNAP: L.QE_OMSG_SNAP,
+                L.QE_STAT_OUTBOX_HEARTBEAT: L.QE_OMSG_HEARTBEAT, L.QE_STAT_OUTBOX_BAD: L.QE_OMSG_BAD}
+    for stat, ty in per_type.items():
+        assert int(folded[stat].item()) == int((t == ty).sum().item()) > 0, ("stat", stat)
+    assert sum(int(folded[stat].item()) for stat in per_type) == n  # the record count

@@ -24,6 +24,7 @@ from tests import ready_model as rdm
 from tests import ready_sim as rsim
 from tests import trace_cluster as tc
 from tests.test_gpu_cluster import DeviceBackend
+from tests.test_gpu_outbox import DeviceRandom, same_list, walk_groups
 from tests.test_gpu_progress import DEV, eng  # noqa: F401
 from tests.test_gpu_trace_cluster import TraceDeviceBackend
 from tests.trace_replay import traces
@@ -456,3 +457,41 @@ def test_closed_loop_storage_from_the_records(eng):  # noqa: F811
     print(f"closed loop: G {p.G}, {p.fault_rounds + p.heal_rounds} rounds, {dict(s.seen)}, "
           f"{s.be.ready_calls} qe_ready calls")
     assert s.seen["truncations"] and s.seen["snapshots"] and s.seen["applied"] and s.seen["hard"]
+
+
+def test_fill_blocks_walk(eng):  # noqa: F811
+    """test_fill_blocks_walk of tests/test_gpu_outbox.py for qe_ready: a quiet
+    batch of one chunk more than the capped fill grid has blocks, with a
+    sparse set of groups that have entries to persist, entries to apply or a
+    new HardState."""
+    e, L = eng, eng._lib
+    G, R, E = walk_groups(), 1, 1
+    rnd = DeviceRandom(G, 0x0EAD)
+    ps = e.ProgressState(G, 1, 1, R, DEV, group_offset=GOFF)
+    ps.run_first[:G], ps.run_term[:G], ps.run_count[:] = 5, 3, 1
+    ps.last_index.copy_(7 + rnd.ints(0, 12))
+    ps.committed.fill_(6)
+    fol = e.Follower(ps)
+    fol.term.copy_(3 + rnd.ints(0, 3))
+    rs = e.ReadyState(ps).reset(ps, fol)
+    rs.applied.copy_(ps.committed)
+    ents, apply, hard = rnd.hit(0.005), rnd.hit(0.005), rnd.hit(0.005)
+    rs.stable.sub_(ents.to(torch.int64))        # Entries: the last one
+    rs.applied.sub_(apply.to(torch.int64))      # CommittedEntries: index 6
+    rs.prev_term.sub_(hard.to(torch.int64))     # a new term: HardState, MustSync
+    cap = int((ents | apply | hard).sum().item()) + 5
+    lists = []
+    for stats in (None, e.stats_buffer(DEV)):
+        rd = e.Ready(ps, cap, E)
+        e.ready(ps, fol, rs, rd, stats=stats)
+        lists.append(rd)
+    n = same_list(lists[0], lists[1], RUNS, E)
+    assert n == cap - 5
+    folded = e.stats_reduce(stats)
+    a = lists[0]
+    want = {0: n,  # QE_STAT_GROUPS: the record count
+            L.QE_STAT_READY_MUST_SYNC: int(((a.flags[:n] & L.QE_RD_MUST_SYNC) != 0).sum().item()),
+            L.QE_STAT_READY_ENTRIES: int(a.ent_count[:n].sum().item()),
+            L.QE_STAT_READY_APPLY: int(a.apply_count[:n].sum().item())}
+    for stat, v in want.items():
+        assert int(folded[stat].item()) == v > 0, ("stat", stat)

@@ -18,7 +18,8 @@ import pytest
 import torch
 
 from tests import replies_model as rm
-from tests.test_gpu_outbox import BIG, CHUNK, DEV, GOFF, SENT, dev, eng, host  # noqa: F401
+from tests.test_gpu_outbox import (BIG, CHUNK, DEV, GOFF, SENT, DeviceRandom, dev, eng,  # noqa: F401
+                                   host, same_list, walk_groups)
 
 pytestmark = pytest.mark.gpu
 CODES = {"F": [0, 1, 2, 3, 4, 5, 6, 7, 15, 16, 17, 18, 19, 20, 255],
@@ -190,3 +191,52 @@ def test_replies_match_model(eng, G, S, fams, density, cap_mode, with_ctx, with_
     # ---- the statistics count every record, past capacity too ----
     for i in range(16):
         assert int(folded[i]) == mstats.get(i, 0), ("stat", i)
+
+
+def test_fill_blocks_walk(eng):  # noqa: F811
+    """test_fill_blocks_walk of tests/test_gpu_outbox.py for qe_replies: every
+    family, sparse, on one chunk more than the capped fill grid has blocks."""
+    e, L = eng, eng._lib
+    G, S = walk_groups(), 1
+    rnd = DeviceRandom(G, 0x0E11)
+    u8 = torch.uint8
+    zero = torch.zeros(G, dtype=u8, device=DEV)
+    ps = e.ProgressState(G, S, 1, 1, DEV, group_offset=GOFF)
+    ps.last_index.copy_(rnd.ints(1, 1 << 40))
+    slots = lambda: rnd.hit(0.05).to(u8)  # noqa: E731  (slot 0, a few that name no slot)
+    f_result = torch.where(rnd.hit(0.01), 2 + rnd.ints(0, 5, u8), zero)
+    s_result = torch.where(rnd.hit(0.005), 2 + rnd.ints(0, 4, u8), zero)
+    codes = torch.tensor([3, 4, 8, 9], dtype=u8, device=DEV)
+    v_result = torch.where(rnd.hit(0.01), codes[rnd.ints(0, 4)], zero)
+    v_type = torch.where(rnd.hit(0.2), torch.full_like(zero, 6), rnd.ints(1, 3, u8))
+    req_to, tn = rnd.ints(0, 256, u8), rnd.hit(0.005).to(u8)
+    follow = (Rows(from_=slots()), Rows(result=f_result, resp_index=rnd.ints(1, 1 << 40),
+                                        reject_hint=rnd.ints(1, 1 << 40),
+                                        resp_log_term=rnd.ints(1, 1 << 40)))
+    snap = (Rows(from_=slots()), Rows(result=s_result, resp_index=rnd.ints(1, 1 << 40)))
+    vote = (Rows(type=v_type, from_=slots()),
+            Rows(result=v_result, resp_term=rnd.ints(1, 1 << 40),
+                 req_log_term=rnd.ints(1, 1 << 40), req_to=req_to))
+    term, f_ctx = rnd.ints(1, 1 << 40), rnd.ints(0, 1 << 31, torch.int32)
+    sends = ((f_result - 2 <= 4).sum() + (s_result - 2 <= 3).sum() + (v_result - 3 <= 1).sum() +
+             ((v_result - 8 <= 1) & ((req_to & 1) != 0)).sum() + tn.sum())  # (u8: 0 - 2 wraps)
+    cap = int(sends.item()) + 5
+    lists = []
+    for stats in (None, e.stats_buffer(DEV)):
+        rp = e.Replies(ps, cap)
+        e.replies(ps, term, rp, follow=follow, snap=snap, vote=vote, timeout_now=tn, f_ctx=f_ctx,
+                  stats=stats)
+        lists.append(rp)
+    n = same_list(lists[0], lists[1], (), 0)
+    folded = e.stats_reduce(stats)
+    t = lists[0].type[:n]
+    per_type = {L.QE_STAT_REPLY_APP_RESP: (L.QE_IMSG_APP_RESP, L.QE_IMSG_APP_RESP_REJECT),
+                L.QE_STAT_REPLY_HEARTBEAT_RESP: (L.QE_IMSG_HEARTBEAT_RESP,),
+                L.QE_STAT_REPLY_VOTE_RESP: (L.QE_IMSG_VOTE_RESP, L.QE_IMSG_PREVOTE_RESP),
+                L.QE_STAT_REPLY_VOTE_REQ: (L.QE_IMSG_VOTE, L.QE_IMSG_PREVOTE),
+                L.QE_STAT_REPLY_TIMEOUT_NOW: (L.QE_IMSG_TIMEOUT_NOW,),
+                L.QE_STAT_REPLY_BAD: (L.QE_RMSG_BAD,)}
+    for stat, types in per_type.items():
+        want = sum(int((t == ty).sum().item()) for ty in types)
+        assert int(folded[stat].item()) == want > 0, ("stat", stat)
+    assert sum(int(folded[stat].item()) for stat in per_type) == n  # the record count
