@@ -17,5 +17,7 @@ from .engine import Timers, tick  # noqa: F401  (raft.tick() over the resident t
 from .engine import (Follower, FollowerOut, LeaderMsgs,  # noqa: F401  (the follower's half)
                      follower_step)
 from .engine import VoteMsgs, VoteOut, Voter, vote_step  # noqa: F401  (elections)
+from .engine import (ReadBook, ReadStates, read_note,  # noqa: F401  (ReadIndex answers)
+                     read_states)
 
 __version__ = "0.1.0"

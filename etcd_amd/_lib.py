@@ -348,6 +348,27 @@ class QeAdvanceOpt(C.Structure):
     _fields_ = [("auto_leave", vp), ("pending_conf_index", vp), ("reserved", u32 * 2)]
 
 
+# qe_read_note / qe_read_states
+QE_RS_STATE, QE_RS_RESP, QE_RS_TERM_COMMIT = 1, 2, 3
+QE_STAT_READ_STATE, QE_STAT_READ_RESP = 4, 6   # = QE_STAT_VOTE_WON / _PENDING
+QE_STAT_READ_TERM_COMMIT = 9                   # = QE_STAT_COMMIT_ADVANCED
+
+
+class QeReadBook(C.Structure):
+    _fields_ = [("req_index", vp), ("req_from", vp)]
+
+
+class QeReadStatesIn(C.Structure):
+    _fields_ = [(k, vp) for k in (
+        "read_released", "term_commit", "term_commit_index", "ri_result", "ri_index", "ri_from",
+        "ri_key")] + [("reserved", u32 * 2)]
+
+
+class QeReadStatesOut(C.Structure):
+    _fields_ = [("capacity", u64)] + [(k, vp) for k in (
+        "group", "kind", "to", "ctx", "index", "key", "count")]
+
+
 QE_BL_NONE, QE_BL_LEADER, QE_BL_NOT_MEMBER, QE_BL_RUNS_FULL = 0, 1, 2, 3
 QE_BL_BCAST = 1
 
@@ -443,6 +464,11 @@ PROTOTYPES = {
     "qe_advance": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeFollower),
                              C.POINTER(QeReadyState), C.POINTER(QeReadyOut),
                              C.POINTER(QeAdvanceOpt), vp, vp]),
+    "qe_read_note": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeReadBook), vp, vp, vp, vp, vp]),
+    "qe_read_states_scratch_bytes": (C.c_size_t, [u64]),
+    "qe_read_states": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeReadBook),
+                                 C.POINTER(QeReadStatesIn), C.POINTER(QeReadStatesOut), vp, vp,
+                                 vp]),
     "qe_gen_groups": (C.c_int, [C.POINTER(QeGroups), C.POINTER(QeGenParams), vp]),
     "qe_apply_append_resps": (C.c_int, [u64, u32, u64, vp, vp, u64, vp, vp, vp, vp, vp]),
     "qe_pack_confstate": (C.c_int, [C.POINTER(QeConfStateCSR), u32, vp, vp, vp, vp, vp, vp]),

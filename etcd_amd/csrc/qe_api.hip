@@ -14,6 +14,7 @@
 #include "qe_inbox.hpp"
 #include "qe_replies.hpp"
 #include "qe_ready.hpp"
+#include "qe_readstates.hpp"
 
 namespace qe {
 
@@ -1294,6 +1295,83 @@ int qe_advance(const qe_progress *p, const qe_follower *f, const qe_ready_state 
   a.cur_state = al_on ? f->state : nullptr;
   a.result = result;
   return dispatch_advance(a, static_cast<hipStream_t>(stream));
+}
+
+int qe_read_note(const qe_progress *p, const qe_read_book *b, const uint8_t *result,
+                 const uint32_t *ctx, const uint64_t *index, const uint8_t *from, void *stream) {
+  if (!p || !b || !result || !ctx || !index || !b->req_index || !b->req_from) return QE_EINVAL;
+  RNoteArgs a{};
+  const int rq = read_queue_cap(p, &a.cap);
+  if (rq) return rq;
+  if (p->num_groups == 0) return QE_OK;
+  a.G = p->num_groups;
+  a.result = result;
+  a.ctx = ctx;
+  a.index = index;
+  a.from = from;
+  a.req_index = b->req_index;
+  a.req_from = b->req_from;
+  return dispatch_read_note(a, static_cast<hipStream_t>(stream));
+}
+
+size_t qe_read_states_scratch_bytes(uint64_t num_groups) {
+  return qe_collect_scratch_bytes(num_groups);
+}
+
+int qe_read_states(const qe_progress *p, const qe_read_book *b, const qe_read_states_in *in,
+                   const qe_read_states_out *out, void *scratch, uint64_t *stats, void *stream) {
+  const int rc = check_progress(p);
+  if (rc) return rc;
+  if (!in || !out || !out->count) return QE_EINVAL;
+  if (in->reserved[0] || in->reserved[1]) return QE_EINVAL;
+  // the released requests are looked up in the book, from the queue's head on
+  if (in->read_released &&
+      (!b || !b->req_index || !b->req_from || !p->read_head || !p->read_count))
+    return QE_EINVAL;
+  if ((in->term_commit && !in->term_commit_index) || (in->ri_result && !in->ri_index))
+    return QE_EINVAL;
+  if (out->capacity && (!out->group || !out->kind || !out->to || !out->ctx || !out->index))
+    return QE_EINVAL;
+  if (!al(scratch, 8) || (p->num_groups && !scratch)) return QE_EINVAL;
+  RSArgs a{};
+  const int rq = read_queue_cap(p, &a.cap);
+  if (rq) return rq;
+  const ScanScratch sc = scan_scratch(scratch, p->num_groups);
+  if (sc.status) return sc.status;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (p->num_groups == 0 || (!in->read_released && !in->term_commit && !in->ri_result))
+    return hip_status(hipMemsetAsync(out->count, 0, sizeof(uint64_t), st));
+  a.G = p->num_groups;
+  a.goff = p->group_offset;
+  a.S = p->num_slots;
+  a.nb = sc.nb;
+  a.offsets = sc.offsets;
+  a.counts = sc.counts;
+  a.read_released = in->read_released;
+  a.term_commit = in->term_commit;
+  a.term_commit_index = in->term_commit_index;
+  a.ri_result = in->ri_result;
+  a.ri_index = in->ri_index;
+  a.ri_from = in->ri_from;
+  a.ri_key = in->ri_key;
+  a.read_head = p->read_head;
+  a.self_slot = p->self_slot;
+  a.read_keys = p->read_keys;
+  a.req_index = b ? b->req_index : nullptr;
+  a.req_from = b ? b->req_from : nullptr;
+  a.ocap = out->capacity;
+  a.o_group = out->group;
+  a.o_kind = out->kind;
+  a.o_to = out->to;
+  a.o_ctx = out->ctx;
+  a.o_index = out->index;
+  a.o_key = out->key;
+  a.stats = stats;
+  int s = dispatch_read_states_count(a, st);
+  if (s) return s;
+  s = launch_scan(sc, out->count, st);
+  if (s) return s;
+  return dispatch_read_states_fill(a, st);
 }
 
 size_t qe_inbox_scratch_bytes(uint64_t num_groups, uint32_t num_slots, uint64_t num_records) {

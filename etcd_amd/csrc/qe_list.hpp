@@ -1,6 +1,6 @@
-// qe_list.hpp — the record-list layer under qe_outbox, qe_replies and qe_ready:
-// what a call that turns per-group rows into a dense, ordered list of records
-// shares with the others.
+// qe_list.hpp — the record-list layer under qe_outbox, qe_replies, qe_ready and
+// qe_read_states: what a call that turns per-group rows into a dense, ordered
+// list of records shares with the others.
 //
 // Three passes over 4096-group chunks (64 tiles, a block of four waves each):
 //   count   the records of each chunk (list_count_block; qe_ready has a count
@@ -16,9 +16,12 @@
 // 64-group tile need and stores them from position tb on, the records of a
 // (kind, slot) at consecutive positions in lane order (ballot + lane_rank), so
 // a wave's stores for one are one contiguous run; every store follows every
-// load of the tile.  Capacity is the output descriptors' num_records
-// (list_room): a record past it is an out-of-range store, dropped, with no
-// branch.  Every access is non-temporal.
+// load of the tile.  (qe_read_states is the exception to both: a group has a
+// run of 0..257 records, so its tile scans the lanes' counts, a lane stores its
+// own run from tb + its prefix on, and the book loads of one position of the
+// runs follow the stores of the position before; qe_readstates.hpp.)  Capacity
+// is the output descriptors' num_records (list_room): a record past it is an
+// out-of-range store, dropped, with no branch.  Every access is non-temporal.
 #pragma once
 #include "qe_step.hpp"
 

@@ -833,10 +833,10 @@ _TORCH = {"u8": torch.uint8, "u32": torch.int32, "u64": torch.int64}
 
 
 class _Records(_Rows):
-    """What the record lists of qe_outbox, qe_replies and qe_ready share: rows
-    of max(1, capacity) records allocated from FIELDS, the rows named in RUNS
-    as [E][capacity] term runs (left out with E = 0), `count` (int64[1]), the
-    cached scratch of the call, and records()."""
+    """What the record lists of qe_outbox, qe_replies, qe_ready and
+    qe_read_states share: rows of max(1, capacity) records allocated from
+    FIELDS, the rows named in RUNS as [E][capacity] term runs (left out with
+    E = 0), `count` (int64[1]), the cached scratch of the call, and records()."""
 
     RUNS = ()
 
@@ -1341,6 +1341,79 @@ def advance(ps, rs, rd, fol=None, auto_leave=None, pending_conf_index=None):
                                               C.byref(r), C.byref(o), C.byref(opt),
                                               _ptr(rd.result), _stream(ps.device)))
     return rd.result
+
+
+class ReadBook(_Rows):
+    """The resident request book of qe_read_book [G][cap] (cap = ps.read_cap,
+    or QE_READ_QUEUE when that is 0): `req_index` int64 storage of
+    readIndexStatus.index and `req_from` u8 (req.From as a slot, >= S = None)
+    of the request with context c of group g, at [g*cap + c % cap]."""
+
+    FIELDS = "req_index:u64 req_from:u8"
+
+    def __init__(self, ps):
+        self.cap = max(_lib.QE_READ_QUEUE, ps.read_cap)
+        n = ps.G * self.cap
+        self.req_index = torch.zeros(n, dtype=torch.int64, device=ps.device)
+        self.req_from = torch.full((n,), 0xFF, dtype=torch.uint8, device=ps.device)
+
+    def struct(self):
+        return _lib.QeReadBook(_ptr(self.req_index), _ptr(self.req_from))
+
+
+class ReadStates(_Records):
+    """The record arrays of qe_read_states (qe_read_states_out) for up to
+    `capacity` records: group / index / key int64 storage of the u64 fields
+    (key=False leaves the row out: not written), kind u8 (QE_RS_*), to u8
+    (0xFF unless kind is QE_RS_RESP), ctx int32, and `count` (int64[1]): the
+    full number of records, which may exceed capacity.  The scratch of the
+    call is cached here."""
+
+    FIELDS = "group:u64 kind:u8 to:u8 ctx:u32 index:u64 key:u64? count:u64"
+
+    def __init__(self, ps, capacity, key=True):
+        self._alloc(ps.device, capacity, without=() if key else ("key",))
+
+    def struct(self):
+        return _lib.QeReadStatesOut(self.capacity,
+                                    *[_ptr(getattr(self, k)) for k in self.ARRAYS])
+
+
+def read_note(ps, book, result, ctx, index, from_=None):
+    """qe_read_note: where result[g] == QE_RI_QUEUED, keep index[g] and
+    from_[g] (None: every request is local) in `book` under the context
+    ctx[g].  result / ctx are the rows read_index returned; `index` is the
+    caller's: the row read_index returned, or a round's term_commit_index for
+    a postponed read added again."""
+    p, b = ps.struct(), book.struct()
+    check("qe_read_note", _lib.lib().qe_read_note(C.byref(p), C.byref(b), _ptr(result), _ptr(ctx),
+                                                  _ptr(index), _ptr(from_), _stream(ps.device)))
+    return book
+
+
+def read_states(ps, book, rs, msgs=None, ri=None, stats=None):
+    """qe_read_states: the answers to ReadIndex requests as a dense list in
+    `rs`, by ascending group: the requests the progress_step just run released
+    (msgs = its PeerMsgs: read_released, term_commit, term_commit_index) and
+    the immediate answers of a read_index call (ri = the tuple it returned,
+    optionally extended: (result, ctx, index[, from_[, key]])).  `book` may be
+    None without msgs.  Nothing resident is written."""
+    lib = _lib.lib()
+    _scratch(rs, ps.device, lib.qe_read_states_scratch_bytes(ps.G))
+    i = _lib.QeReadStatesIn()
+    if msgs is not None:
+        i.read_released = _ptr(msgs.read_released)
+        i.term_commit, i.term_commit_index = _ptr(msgs.term_commit), _ptr(msgs.term_commit_index)
+    if ri is not None:
+        ri = tuple(ri) + (None,) * (5 - len(ri))
+        i.ri_result, i.ri_index, i.ri_from, i.ri_key = (_ptr(ri[0]), _ptr(ri[2]), _ptr(ri[3]),
+                                                        _ptr(ri[4]))
+    p, o = ps.struct(), rs.struct()
+    b = book.struct() if book is not None else None
+    check("qe_read_states", lib.qe_read_states(C.byref(p), C.byref(b) if b is not None else None,
+                                               C.byref(i), C.byref(o), _ptr(rs.scratch),
+                                               _ptr(stats), _stream(ps.device)))
+    return rs
 
 
 class Inbox(_Rows):

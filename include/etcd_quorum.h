@@ -574,7 +574,9 @@ int qe_progress_step(const qe_progress *p, const qe_peer_msgs *m, uint64_t *stat
  *     capacity the host chose; up to QE_READ_CAP_MAX).
  * Needs p->read_acks / read_head / read_count unless every result is
  * RESPOND or POSTPONED (lease_based).  ctx and index may be NULL; they are
- * written only where they apply.  Groups without a request: result 0. */
+ * written only where they apply.  Groups without a request: result 0.
+ * qe_read_note keeps the index and the origin of a QUEUED request on the
+ * device, and qe_read_states lists the answers (below, after qe_ready). */
 #define QE_RI_NONE 0
 #define QE_RI_RESPOND 1
 #define QE_RI_POSTPONED 2
@@ -2151,7 +2153,7 @@ int qe_replies(const qe_progress *p, const qe_replies_in *in, const qe_replies_o
  *     or snap_pending != 0, or Entries is non-empty, or CommittedEntries is
  *     non-empty, or pending[g] != 0 (an optional row for what this call
  *     cannot see: messages, which qe_outbox / qe_replies list, and
- *     ReadStates).
+ *     ReadStates, which qe_read_states lists).
  *  7. Every listed record: group = group_offset + g, term, commit =
  *     committed, vote and lead (0xFF for None), state, and flags: QE_RD_SOFT
  *     where soft_changed, QE_RD_HARD where !hard_empty && hard_changed (only
@@ -2297,6 +2299,138 @@ int qe_ready(const qe_progress *p, const qe_follower *f, const qe_ready_state *r
 /* f and opt may be NULL (no AutoLeave check). */
 int qe_advance(const qe_progress *p, const qe_follower *f, const qe_ready_state *rs,
                const qe_ready_out *list, const qe_advance_opt *opt, uint8_t *result, void *stream);
+
+/* qe_read_note / qe_read_states (additive in ABI 8): the answers to ReadIndex
+ * requests as a dense device list -- the ReadStates of a Ready and the
+ * MsgReadIndexResp messages, the part of a Ready that qe_ready (rule 6) leaves
+ * to its `pending` row.  The queue of qe_progress (read_acks / read_head /
+ * read_count / read_keys) holds a pending request's acks and key; what
+ * readOnly.pendingReadIndex keeps besides (readIndexStatus.index and the
+ * request's origin, raft/read_only.go:29-37) is resident in the request book,
+ * so a host no longer keeps a map context -> (index, from) per group, copies
+ * read_released / term_commit / term_commit_index [G] every step, or decides
+ * responseToReadIndexReq (raft/raft.go:1737-1751) itself: it copies min(*count,
+ * capacity) records.
+ *
+ * qe_read_book, two resident rows [G][cap], read-write, device; cap =
+ * p->read_cap, or QE_READ_QUEUE when read_cap is 0.  The request with context c
+ * of group g is at [g*cap + c % cap], the addressing of p->read_keys:
+ *   req_index   readIndexStatus.index: the read index of the request
+ *   req_from    req.From as a slot; >= num_slots = None (a local request)
+ * An entry is valid while its context is pending and stays readable after its
+ * release until a later request takes the slot.  The book needs no clearing
+ * at a stepdown or in qe_become_leader: only contexts the queue names are read.
+ *
+ * qe_read_note: addRequest's bookkeeping half (read_only.go:56-63).  It takes
+ * the rows a qe_read_index call wrote, result / ctx [G], and the caller's index
+ * [G] and from [G] (NULL = every request is local: 0xFF is stored).  Where
+ * result[g] == QE_RI_QUEUED it stores index[g] and from[g] at ctx[g] % cap;
+ * every other result writes nothing (a QE_RI_DUPLICATE keeps the first
+ * request's entry, as addRequest does).  `index` is the caller's row on
+ * purpose: a postponed read re-added after term_commit is noted at that
+ * round's term_commit_index, not at the index the re-adding qe_read_index
+ * returns (see qe_read_index; raft.go:1813-1834).  Of p it reads num_groups and
+ * read_cap.  QE_EINVAL: a NULL p / b / result / ctx / index or a NULL row of b;
+ * a nonzero reserved3; read_acks with a read_cap above QE_READ_QUEUE and no
+ * read_ovf (as wherever the queue's capacity is read); QE_ERANGE: read_cap
+ * outside 0, QE_READ_QUEUE..QE_READ_CAP_MAX.  num_groups == 0 is QE_OK.
+ *
+ * qe_read_states.  Of p it reads num_groups (G), group_offset, num_slots (S),
+ * read_cap, read_head, self_slot (NULL: no slot is the group's own) and
+ * read_keys (NULL: keys not tracked).  Every row of `in` is optional:
+ * read_released / term_commit / term_commit_index are the output rows of the
+ * qe_progress_step just run, ri_result / ri_index / ri_key / ri_from the rows of
+ * a qe_read_index call and its requests' origins.
+ *  1. Ordering.  Records go by ascending group; within a group: the released
+ *     requests in queue order (oldest first, as readOnly.advance returns them,
+ *     read_only.go:85-112), then the TERM_COMMIT record, then the record of an
+ *     immediate answer.
+ *  2. Released requests.  k = read_released[g] requests were released; their
+ *     contexts are read_head[g] - k + j (mod 2^32), j < k, with read_head read
+ *     as it is after the step.  Contexts of a pending queue never cross 0
+ *     (qe_read_index refuses with QE_RI_FULL), so this is exact.  Each yields
+ *     ctx = c, index = req_index[g*cap + c % cap] and key = read_keys[g*cap +
+ *     c % cap] when keys are tracked, else 0.
+ *  3. Kind.  With f = req_from[g*cap + c % cap]: f >= num_slots, or f ==
+ *     self_slot[g], gives QE_RS_STATE with to = 0xFF (req.From == None ||
+ *     req.From == r.id: r.readStates gets ReadState{Index, RequestCtx});
+ *     otherwise QE_RS_RESP with to = f (MsgReadIndexResp{To: req.From, Index,
+ *     Entries: req.Entries}).
+ *  4. TERM_COMMIT.  term_commit[g] != 0 gives one QE_RS_TERM_COMMIT record
+ *     with index = term_commit_index[g], to = 0xFF, ctx = 0, key = 0: the host
+ *     adds its postponed reads again (qe_read_index) and notes them at `index`.
+ *  5. Immediate answers.  ri_result[g] == QE_RI_RESPOND (IsSingleton or
+ *     lease-based, raft.go:1080-1084, :1838-1841) gives one record by rule 3
+ *     with f = ri_from[g] (a NULL ri_from: None), index = ri_index[g], key =
+ *     ri_key[g] (0 with a NULL ri_key) and ctx = 0.
+ *  6. Capacity.  *count is the full number of records; nothing at or past
+ *     min(*count, capacity) is touched in any output array (qe_outbox rule 3).
+ *  7. State.  Nothing resident is written.
+ *  8. Call order.  The call runs after the step whose rows it takes and
+ *     before the next qe_read_index on the same state: a later request may
+ *     take a released slot of the book (and of read_keys).
+ *  9. stats (optional), over every record, those past capacity too:
+ *     QE_STAT_GROUPS += groups with at least one record; QE_STAT_READ_STATE /
+ *     _RESP / _TERM_COMMIT += records by kind; QE_STAT_CHECKSUM += h3 per
+ *     record, h1 = mix64(group * 0x9E3779B97F4A7C15 ^ 0xE7037ED1A0B428DB ^ kind
+ *     << 56 ^ to << 48 ^ ctx), h2 = mix64(h1 ^ index), h3 = mix64(h2 ^ key), as
+ *     the record holds them (key 0 where it has none).
+ * `count` and every array of qe_read_states_out are DEVICE pointers; `key` may
+ * be NULL (not written).  scratch is qe_read_states_scratch_bytes(num_groups)
+ * bytes of device memory, 8-B aligned (the chunk offsets and counts of
+ * qe_collect).  Stream-ordered: three kernels (count, the scan of qe_collect,
+ * fill), no host synchronisation.
+ * QE_EINVAL: a NULL p / in / out / count / scratch (with num_groups > 0);
+ * read_released with a NULL b, a NULL row of b, or a NULL read_head /
+ * read_count; term_commit without term_commit_index; ri_result without
+ * ri_index; capacity > 0 with a NULL group / kind / to / ctx / index; a nonzero
+ * reserved field; num_slots outside 1..16; read_acks with a read_cap above
+ * QE_READ_QUEUE and no read_ovf; scratch not 8-B aligned.  QE_ERANGE: a
+ * read_cap out of range; more chunks than a launch holds (qe_ready's check).
+ * Every argument check runs before the first HIP call.  num_groups == 0, or
+ * every row of `in` NULL, is QE_OK with *count = 0. */
+#define QE_RS_STATE 1        /* local ReadState{Index, RequestCtx} */
+#define QE_RS_RESP 2         /* MsgReadIndexResp{To, Index, Entries = the request's} */
+#define QE_RS_TERM_COMMIT 3  /* releasePendingReadIndexMessages fired: re-add the
+                                postponed reads at `index` */
+#define QE_STAT_READ_STATE QE_STAT_VOTE_WON             /* qe_read_states: records by kind */
+#define QE_STAT_READ_RESP QE_STAT_VOTE_PENDING
+#define QE_STAT_READ_TERM_COMMIT QE_STAT_COMMIT_ADVANCED
+
+typedef struct qe_read_book {
+  uint64_t *req_index;   /* [G][cap] rw: readIndexStatus.index of the request with context c,
+                            at [g*cap + c % cap] (the addressing of qe_progress.read_keys) */
+  uint8_t  *req_from;    /* [G][cap] rw: req.From as a slot; >= num_slots = None (local) */
+} qe_read_book;
+
+typedef struct qe_read_states_in {
+  const uint8_t  *read_released;      /* [G] or NULL: qe_peer_msgs.read_released of the step just run */
+  const uint8_t  *term_commit;        /* [G] or NULL */
+  const uint64_t *term_commit_index;  /* [G], with term_commit */
+  const uint8_t  *ri_result;          /* [G] or NULL: a qe_read_index call's result row */
+  const uint64_t *ri_index;           /* [G], with ri_result */
+  const uint8_t  *ri_from;            /* [G] or NULL (local), with ri_result */
+  const uint64_t *ri_key;             /* [G] or NULL, with ri_result */
+  uint32_t reserved[2];               /* must be 0 */
+} qe_read_states_in;
+
+typedef struct qe_read_states_out {
+  uint64_t capacity;
+  uint64_t *group;     /* [capacity] group_offset + g */
+  uint8_t  *kind;      /* [capacity] QE_RS_* */
+  uint8_t  *to;        /* [capacity] slot of a MsgReadIndexResp; 0xFF otherwise */
+  uint32_t *ctx;       /* [capacity] context number; 0 for records that have none */
+  uint64_t *index;     /* [capacity] ReadState.Index / m.Index / term_commit_index */
+  uint64_t *key;       /* [capacity] or NULL: the request's key (read_keys / ri_key), else 0 */
+  uint64_t *count;     /* device: the full number, may exceed capacity */
+} qe_read_states_out;
+
+int qe_read_note(const qe_progress *p, const qe_read_book *b, const uint8_t *result,
+                 const uint32_t *ctx, const uint64_t *index, const uint8_t *from, void *stream);
+size_t qe_read_states_scratch_bytes(uint64_t num_groups);
+/* b may be NULL without read_released. */
+int qe_read_states(const qe_progress *p, const qe_read_book *b, const qe_read_states_in *in,
+                   const qe_read_states_out *out, void *scratch, uint64_t *stats, void *stream);
 
 /* ---- statistics -------------------------------------------------------- */
 
