@@ -369,6 +369,39 @@ class QeReadStatesOut(C.Structure):
         "group", "kind", "to", "ctx", "index", "key", "count")]
 
 
+# qe_requests
+QE_QMSG_TRANSFER_LEADER = 10   # = QE_IMSG_TRANSFER_LEADER
+QE_QMSG_PROP, QE_QMSG_READ_INDEX, QE_QMSG_READ_INDEX_RESP = 17, 18, 19
+(QE_QD_ROUTED, QE_QD_STEPDOWN, QE_QD_DEFERRED, QE_QD_DROP_LOWER_TERM, QE_QD_NO_ARM,
+ QE_QD_FORWARDED, QE_QD_READ_STATE, QE_QD_PROP_DROPPED, QE_QD_NO_LEADER,
+ QE_QD_REF_PANIC) = range(1, 11)
+QE_QD_BAD = 255
+QE_QO_FWD, QE_QO_READ_STATE, QE_QO_PROP_DROPPED = 1, 2, 3
+QE_REQ_NO_FORWARD = 1
+QE_STAT_REQ_BAD, QE_STAT_REQ_NO_ARM, QE_STAT_REQ_NO_LEADER = 1, 2, 3   # = QE_STAT_COMMIT_*
+QE_STAT_REQ_ROUTED, QE_STAT_REQ_LOWER_TERM, QE_STAT_REQ_DEFERRED = 4, 5, 6  # = QE_STAT_VOTE_*
+QE_STAT_REQ_FORWARDED, QE_STAT_REQ_PROP_DROPPED = 7, 8   # = QE_STAT_GRANTED / _REJECTED
+QE_STAT_REQ_READ_STATE = 9     # = QE_STAT_COMMIT_ADVANCED
+QE_STAT_REQ_REF_PANIC = 10     # = QE_STAT_READ_RELEASED
+QE_STAT_REQ_STEPDOWN = 13      # = QE_STAT_STEPDOWNS
+
+
+class QeRequestsIn(C.Structure):
+    _fields_ = [("num_records", u64), ("max_cc", u32), ("flags", u32)] + [(k, vp) for k in (
+        "group", "type", "from_", "term", "index", "key", "num_entries", "payload", "cc_count",
+        "cc_pos", "cc_leave", "cc_size")] + [("reserved", u64)]
+
+
+class QeRequestsOut(C.Structure):
+    _fields_ = [(k, vp) for k in (
+        "p_num_entries", "p_payload", "p_cc_count", "p_cc_pos", "p_cc_leave", "p_cc_size")] + [
+        ("cc_stride", u64)] + [(k, vp) for k in (
+            "ri_request", "ri_key", "ri_from", "v_type", "v_from", "v_term", "v_index",
+            "v_log_term", "v_flags", "r_type", "p_src", "ri_src", "v_src", "r_src", "disposition",
+            "deferred", "deferred_count")] + [("capacity", u64)] + [(k, vp) for k in (
+                "group", "kind", "type", "to", "from_", "term", "index", "key", "src", "count")]
+
+
 QE_BL_NONE, QE_BL_LEADER, QE_BL_NOT_MEMBER, QE_BL_RUNS_FULL = 0, 1, 2, 3
 QE_BL_BCAST = 1
 
@@ -469,6 +502,9 @@ PROTOTYPES = {
     "qe_read_states": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeReadBook),
                                  C.POINTER(QeReadStatesIn), C.POINTER(QeReadStatesOut), vp, vp,
                                  vp]),
+    "qe_requests_scratch_bytes": (C.c_size_t, [u64, u64]),
+    "qe_requests": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeFollower),
+                              C.POINTER(QeRequestsIn), C.POINTER(QeRequestsOut), vp, vp, vp]),
     "qe_gen_groups": (C.c_int, [C.POINTER(QeGroups), C.POINTER(QeGenParams), vp]),
     "qe_apply_append_resps": (C.c_int, [u64, u32, u64, vp, vp, u64, vp, vp, vp, vp, vp]),
     "qe_pack_confstate": (C.c_int, [C.POINTER(QeConfStateCSR), u32, vp, vp, vp, vp, vp, vp]),

@@ -15,6 +15,7 @@
 #include "qe_replies.hpp"
 #include "qe_ready.hpp"
 #include "qe_readstates.hpp"
+#include "qe_requests.hpp"
 
 namespace qe {
 
@@ -1482,6 +1483,143 @@ int qe_inbox(const qe_progress *p, const qe_follower *f, const qe_inbox_in *in,
   s = launch_scan(sc, out->deferred_count, st);
   if (s || !n) return s;
   return dispatch_inbox_deferred(a, nb, st);
+}
+
+size_t qe_requests_scratch_bytes(uint64_t num_groups, uint64_t num_records) {
+  return static_cast<size_t>(4 * num_groups + 2 * num_records +
+                             2 * qe_collect_scratch_bytes(num_records));
+}
+
+int qe_requests(const qe_progress *p, const qe_follower *f, const qe_requests_in *in,
+                const qe_requests_out *out, void *scratch, uint64_t *stats, void *stream) {
+  const int rc = check_progress(p);
+  if (rc) return rc;
+  if (!f || !in || !out || !f->term || !f->state || !f->lead || !p->self_slot) return QE_EINVAL;
+  if (in->reserved || (in->flags & ~QE_REQ_NO_FORWARD)) return QE_EINVAL;
+  if (p->num_groups && p->stride < p->num_groups) return QE_EINVAL;
+  if (in->max_cc > QE_PROP_MAX_CC) return QE_EINVAL;
+  if (in->max_cc &&
+      (out->cc_stride < p->num_groups || !out->p_cc_count || !out->p_cc_pos || !out->p_cc_leave ||
+       !out->p_cc_size || (in->cc_count && (!in->cc_pos || !in->cc_leave || !in->cc_size))))
+    return QE_EINVAL;
+  const uint64_t n = in->num_records;
+  if (n && (!in->group || !in->type || !in->from || !in->term || !in->index || !in->key))
+    return QE_EINVAL;
+  if (!out->p_num_entries || !out->ri_request || !out->ri_key || !out->ri_from || !out->v_type ||
+      !out->v_from || !out->v_term || !out->v_index || !out->v_log_term || !out->r_type ||
+      !out->disposition || !out->deferred || !out->deferred_count || !out->count)
+    return QE_EINVAL;
+  if (out->capacity && (!out->group || !out->kind || !out->type || !out->to || !out->from ||
+                        !out->term || !out->index || !out->key || !out->src))
+    return QE_EINVAL;
+  if (p->num_groups && !scratch) return QE_EINVAL;
+  if (!al(scratch, 8)) return QE_EINVAL;
+  if (n > 0xFFFFFFF0ull) return QE_ERANGE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (p->num_groups == 0) {
+    const int s = hip_status(hipMemsetAsync(out->deferred_count, 0, sizeof(uint64_t), st));
+    return s ? s : hip_status(hipMemsetAsync(out->count, 0, sizeof(uint64_t), st));
+  }
+  RQArgs a{};
+  a.G = p->num_groups;
+  a.goff = p->group_offset;
+  a.stride = p->stride;
+  a.n = n;
+  a.cc_stride = out->cc_stride;
+  a.S = p->num_slots;
+  a.max_cc = in->max_cc;
+  a.flags = in->flags;
+  a.fterm = f->term;
+  a.fstate = f->state;
+  a.flead = f->lead;
+  a.group = in->group;
+  a.type = in->type;
+  a.from = in->from;
+  a.term = in->term;
+  a.key = in->key;
+  a.num_entries = in->num_entries;
+  a.payload = in->payload;
+  a.cc_count = in->cc_count;
+  a.cc_pos = in->cc_count ? in->cc_pos : nullptr;
+  a.cc_leave = in->cc_count ? in->cc_leave : nullptr;
+  a.cc_size = in->cc_count ? in->cc_size : nullptr;
+  a.p_num_entries = out->p_num_entries;
+  a.p_payload = out->p_payload;
+  a.p_cc_count = out->p_cc_count;
+  a.p_cc_pos = out->p_cc_pos;
+  a.p_cc_leave = out->p_cc_leave;
+  a.p_cc_size = out->p_cc_size;
+  a.ri_request = out->ri_request;
+  a.ri_key = out->ri_key;
+  a.ri_from = out->ri_from;
+  a.v_type = out->v_type;
+  a.v_from = out->v_from;
+  a.v_term = out->v_term;
+  a.v_index = out->v_index;
+  a.v_log_term = out->v_log_term;
+  a.v_flags = out->v_flags;
+  a.r_type = out->r_type;
+  a.p_src = out->p_src;
+  a.ri_src = out->ri_src;
+  a.v_src = out->v_src;
+  a.r_src = out->r_src;
+  a.disposition = out->disposition;
+  a.stats = stats;
+  // scratch: the chunk offsets of the two lists (u64, n is in range: its chunks fit a
+  // launch), their chunk counts (u32), the words stop [G], the flags dflag and okind [n]
+  const uint64_t nb = (n + kCollectChunk - 1) / kCollectChunk;
+  uint64_t *off = static_cast<uint64_t *>(scratch);
+  uint32_t *cnt = reinterpret_cast<uint32_t *>(off + 2 * nb);
+  const ScanScratch sd{QE_OK, nb, off, cnt}, so{QE_OK, nb, off + nb, cnt + nb};
+  a.stop = cnt + 2 * nb;
+  a.dflag = reinterpret_cast<uint8_t *>(a.stop + a.G);
+  a.okind = a.dflag + n;
+  int s = dispatch_requests_init(a, st);
+  if (s) return s;
+  if (n) {
+    s = dispatch_requests_passes(a, st);
+    if (s) return s;
+    const dim3 grid(static_cast<unsigned>((nb + kCountWaves - 1) / kCountWaves));
+    hipLaunchKernelGGL(k_collect_count, grid, dim3(kBlock), 0, st, a.dflag, n, al(a.dflag, 16), nb,
+                       sd.counts);
+    hipLaunchKernelGGL(k_collect_count, grid, dim3(kBlock), 0, st, a.okind, n, al(a.okind, 16), nb,
+                       so.counts);
+  }
+  s = launch_scan(sd, out->deferred_count, st);
+  if (s) return s;
+  s = launch_scan(so, out->count, st);
+  if (s || !n) return s;
+  RQList l{};
+  l.G = n;
+  l.nb = nb;
+  l.goff = p->group_offset;
+  l.offsets = so.offsets;
+  l.flag = a.okind;
+  l.fterm = f->term;
+  l.flead = f->lead;
+  l.self_slot = p->self_slot;
+  l.S = p->num_slots;
+  l.group = in->group;
+  l.type = in->type;
+  l.from = in->from;
+  l.index = in->index;
+  l.key = in->key;
+  l.cap = out->capacity;
+  l.o_group = out->group;
+  l.o_kind = out->kind;
+  l.o_type = out->type;
+  l.o_to = out->to;
+  l.o_from = out->from;
+  l.o_term = out->term;
+  l.o_index = out->index;
+  l.o_key = out->key;
+  l.o_src = out->src;
+  s = dispatch_requests_out(l, st);
+  if (s) return s;
+  l.offsets = sd.offsets;
+  l.flag = a.dflag;
+  l.deferred = out->deferred;
+  return dispatch_requests_deferred(l, st);
 }
 
 int qe_stats_reduce(const uint64_t *stats, uint64_t *out, void *stream) {

@@ -1556,6 +1556,121 @@ def inbox(ps, fol, ib, lm, sm, vm, pm, tick_action=None, stats=None):
     return ib
 
 
+class Requests(_Records):
+    """The request list of qe_requests (qe_requests_in) for up to
+    `list_capacity` records, its per-record outputs and its output list for up
+    to `capacity` records (default: list_capacity).  The list rows are q_group /
+    q_term / q_index / q_key / q_payload int64 storage of the u64 fields,
+    q_type (QE_QMSG_*) / q_from_ (0xFF = None) / q_cc_count u8, q_num_entries
+    int32 and, with max_cc > 0, q_cc_pos / q_cc_size int32 and q_cc_leave u8
+    laid out [max_cc][n] for the n records loaded.  Per record: `disposition`
+    u8 (QE_QD_*) and the deferred positions (`deferred`).  The rows that have
+    no home in Proposals / PeerMsgs / VoteMsgs are kept here: ri_request u8,
+    ri_key int64 and ri_from u8 [G], and with src=True the source position rows
+    p_src / ri_src / v_src [G] and r_src [S][stride] (int32).  The output list
+    (records()) is group / term / index / key int64 storage, kind (QE_QO_*) /
+    type / to / from_ u8, src int32 and `count` (int64[1]): the full number,
+    which may exceed capacity.  The scratch of the call is cached here."""
+
+    FIELDS = "group:u64 kind:u8 type:u8 to:u8 from_:u8 term:u64 index:u64 key:u64 src:u32 count:u64"
+    LIST = {"group": "u64", "type": "u8", "from_": "u8", "term": "u64", "index": "u64",
+            "key": "u64", "num_entries": "u32", "payload": "u64", "cc_count": "u8"}
+    CC = {"cc_pos": "u32", "cc_leave": "u8", "cc_size": "u32"}
+
+    def __init__(self, ps, list_capacity, capacity=None, max_cc=0, src=True):
+        if not 0 <= int(max_cc) <= _lib.QE_PROP_MAX_CC:
+            raise ValueError("max_cc must be 0..QE_PROP_MAX_CC")
+        dev, i64, i32, u8 = ps.device, torch.int64, torch.int32, torch.uint8
+        self._alloc(dev, list_capacity if capacity is None else capacity)
+        self.list_capacity, self.max_cc, self.n = int(list_capacity), int(max_cc), 0
+        c = max(1, self.list_capacity)
+        for k, kind in self.LIST.items():
+            setattr(self, "q_" + k, torch.zeros(c, dtype=_TORCH[kind], device=dev))
+        for k, kind in self.CC.items():
+            setattr(self, "q_" + k, torch.zeros(self.max_cc * c, dtype=_TORCH[kind], device=dev)
+                    if self.max_cc else None)
+        self.ri_request = torch.zeros(ps.G, dtype=u8, device=dev)
+        self.ri_key = torch.zeros(ps.G, dtype=i64, device=dev)
+        self.ri_from = torch.zeros(ps.G, dtype=u8, device=dev)
+        self.disposition = torch.zeros(c, dtype=u8, device=dev)
+        self.deferred_pos = torch.zeros(c, dtype=i32, device=dev)
+        self.deferred_count = torch.zeros(1, dtype=i64, device=dev)
+        self.p_src = self.ri_src = self.v_src = self.r_src = None
+        if src:
+            self.p_src = torch.zeros(ps.G, dtype=i32, device=dev)
+            self.ri_src = torch.zeros(ps.G, dtype=i32, device=dev)
+            self.v_src = torch.zeros(ps.G, dtype=i32, device=dev)
+            self.r_src = torch.zeros(ps.S * ps.stride, dtype=i32, device=dev)
+
+    def load_host(self, **arrays):
+        """The list from numpy arrays of the unsigned types (`from` is accepted
+        for `from_`), replacing the one loaded before; cc_pos / cc_leave /
+        cc_size are [max_cc][m] for the m records given; a field left out is 0."""
+        arrays = {("from_" if k == "from" else k): v for k, v in arrays.items()}
+        for k in arrays:
+            if k not in self.LIST and k not in self.CC:
+                raise KeyError(k)
+        m = len(arrays["group"])
+        if m > self.list_capacity:
+            raise ValueError("the list does not fit the Requests")
+        for k in list(self.LIST) + list(self.CC):
+            dst = getattr(self, "q_" + k)
+            size = m * (self.max_cc if k in self.CC else 1)
+            if dst is None or not size:
+                continue
+            if k not in arrays:
+                dst[:size].zero_()
+                continue
+            a = np.ascontiguousarray(arrays[k])
+            a = a.view(_SIGNED.get(a.dtype, a.dtype)).reshape(size)
+            dst[:size].copy_(torch.from_numpy(a.copy()).to(dst.device).to(dst.dtype))
+        self.n = m
+        return self
+
+    @property
+    def deferred(self):
+        """The positions of the DEFERRED records, ascending (numpy uint32)."""
+        count = int(self.deferred_count.item())
+        return self.deferred_pos[:count].cpu().numpy().view(np.uint32)
+
+    def dispositions(self):
+        return self.disposition[: self.n].cpu().numpy()
+
+
+def requests(ps, fol, rq, props, pm, vm, stats=None, no_forward=False):
+    """qe_requests: the request list of `rq` handled as raft.Step would on each
+    record's receiver.  The leader-side rows go into the Proposals `props`
+    (num_entries, payload and the conf-change rows), rq.ri_request / ri_key /
+    ri_from (for read_index, read_note and read_states), pm.type of the
+    PeerMsgs `pm` (QE_MSG_TRANSFER_LEADER) and the VoteMsgs `vm` (a higher
+    term); the steps then run in the order propose, read_index, read_note,
+    progress_step, vote_step, read_states.  no_forward is
+    Config.DisableProposalForwarding.  The dispositions, the deferred
+    positions and the output list are left in `rq`."""
+    if props.max_cc != rq.max_cc:
+        raise ValueError("the Proposals and the Requests differ in max_cc")
+    lib = _lib.lib()
+    _scratch(rq, ps.device, lib.qe_requests_scratch_bytes(ps.G, rq.n),
+             grow=lib.qe_requests_scratch_bytes(ps.G, max(1, rq.list_capacity)))
+    p, f = ps.struct(), fol.struct()
+    i = _lib.QeRequestsIn(
+        rq.n, rq.max_cc, _lib.QE_REQ_NO_FORWARD if no_forward else 0, _ptr(rq.q_group),
+        _ptr(rq.q_type), _ptr(rq.q_from_), _ptr(rq.q_term), _ptr(rq.q_index), _ptr(rq.q_key),
+        _ptr(rq.q_num_entries), _ptr(rq.q_payload), _ptr(rq.q_cc_count), _ptr(rq.q_cc_pos),
+        _ptr(rq.q_cc_leave), _ptr(rq.q_cc_size), 0)
+    o = _lib.QeRequestsOut(
+        _ptr(props.num_entries), _ptr(props.payload), _ptr(props.cc_count), _ptr(props.cc_pos),
+        _ptr(props.cc_leave), _ptr(props.cc_size), props.G,
+        _ptr(rq.ri_request), _ptr(rq.ri_key), _ptr(rq.ri_from),
+        _ptr(vm.type), _ptr(vm.from_), _ptr(vm.term), _ptr(vm.index), _ptr(vm.log_term),
+        _ptr(vm.flags), _ptr(pm.type), _ptr(rq.p_src), _ptr(rq.ri_src), _ptr(rq.v_src),
+        _ptr(rq.r_src), _ptr(rq.disposition), _ptr(rq.deferred_pos), _ptr(rq.deferred_count),
+        rq.capacity, *[_ptr(getattr(rq, k)) for k in rq.ARRAYS])
+    check("qe_requests", lib.qe_requests(C.byref(p), C.byref(f), C.byref(i), C.byref(o),
+                                         _ptr(rq.scratch), _ptr(stats), _stream(ps.device)))
+    return rq
+
+
 class Proposals:
     """One MsgProp per group for qe_propose (qe_proposals, ABI 6):
     num_entries [G] (0 = none), payload [G] (sum of the non-conf-change

@@ -2432,6 +2432,213 @@ size_t qe_read_states_scratch_bytes(uint64_t num_groups);
 int qe_read_states(const qe_progress *p, const qe_read_book *b, const qe_read_states_in *in,
                    const qe_read_states_out *out, void *scratch, uint64_t *stats, void *stream);
 
+/* qe_requests (additive in ABI 8): a list of client requests handled as
+ * raft.Step would on their receiver -- the one way into Step the calls above
+ * leave to the host.  Propose, ReadIndex and TransferLeadership may be called
+ * on any node, and a MsgReadIndexResp comes back to a follower; the engine has
+ * the leader's arms (qe_propose, qe_read_index, QE_MSG_TRANSFER_LEADER of
+ * qe_progress_step).  This call adds stepFollower's arms (raft/raft.go:
+ * 1423-1432, :1445-1451, :1458-1470), stepCandidate's MsgProp drop (:1387-1389),
+ * Step's term preamble for the two types that carry a term, and the routing of
+ * the list into the leader-side rows, so a host keeps neither state nor lead
+ * off the device and builds no G-sized row on the CPU.  It READS the list,
+ * f->term, f->state and f->lead; of p it reads num_groups (G), group_offset,
+ * num_slots (S), stride and self_slot (required) and nothing else.  It writes
+ * nothing resident: only the rows of qe_requests_out, which the caller points
+ * at the buffers it then passes on (rule 7), the dispositions and two dense
+ * lists.
+ *
+ * The list is in arrival order; a record's position i is its rank.  `from` is
+ * a slot in the receiver's numbering, or 0xFF = None: a local call without
+ * From.  `term` is 0 for a local call and for a request forwarded without a
+ * term.  `key` is the 64-bit request key qe_read_index / read_keys use as
+ * RequestCtx.  The types continue the QE_IMSG_* numbering, so a transport has
+ * one record format; qe_inbox itself still answers QE_ID_BAD for 17..19.
+ *
+ *  1. BAD.  A record gets QE_QD_BAD when its group is outside [group_offset,
+ *     group_offset + G); its type is none of QE_QMSG_*; its from is neither
+ *     < S nor 0xFF; it is a PROP with num_entries == 0 (stepLeader panics on
+ *     an empty MsgProp, raft.go:1020-1022); it is a PROP or READ_INDEX with
+ *     term != 0 (send never attaches one, :410-416); or it is a
+ *     TRANSFER_LEADER with from == 0xFF (m.From is the transferee).  It takes
+ *     no further part and is never deferred.
+ *  2. Preamble.  A record with term == 0 is local and passes (:850-851).
+ *     Otherwise, with r.Term = f->term[g]:
+ *     a. term < r.Term: QE_QD_DROP_LOWER_TERM (:883-919: none of these types
+ *        is answered);
+ *     b. term > r.Term: QE_QD_STEPDOWN.  The vote rows at [g] get v_type =
+ *        QE_VMSG_VOTE_RESP with from, term, index and log_term 0 and flags
+ *        QE_VMF_REJECT (qe_inbox rule 6c: becomeFollower(m.Term, None) runs in
+ *        qe_vote_step).  What stepFollower does next is decided at once: a
+ *        READ_INDEX_RESP also yields its READ_STATE output record (rule 5); a
+ *        TRANSFER_LEADER yields nothing, because lead is None after the
+ *        stepdown (:1446-1449).
+ *  3. By role (f->state[g]), for a record that passed rule 2:
+ *     a. QE_STATE_LEADER.  PROP: QE_QD_ROUTED into the proposal rows at [g]:
+ *        p_num_entries, p_payload, p_cc_count and all max_cc conf-change rows
+ *        p_cc_pos / p_cc_leave / p_cc_size at [k*cc_stride+g] (zeros included).
+ *        READ_INDEX: ROUTED into ri_request[g] = 1, ri_key[g] = key, ri_from[g]
+ *        = from.  TRANSFER_LEADER: ROUTED into r_type[from*stride+g] =
+ *        QE_MSG_TRANSFER_LEADER.  READ_INDEX_RESP: QE_QD_NO_ARM (stepLeader has
+ *        no arm for it).
+ *     b. QE_STATE_CANDIDATE / _PRE_CANDIDATE.  PROP: QE_QD_PROP_DROPPED
+ *        (ErrProposalDropped, :1387-1389); every other type: QE_QD_NO_ARM.
+ *     c. Any other state is a follower, with lead = f->lead[g] (>= S = None).
+ *        PROP: no lead, or QE_REQ_NO_FORWARD (Config.
+ *        DisableProposalForwarding), gives QE_QD_PROP_DROPPED (:1424-1430);
+ *        otherwise QE_QD_FORWARDED (:1431-1432).  READ_INDEX: no lead gives
+ *        QE_QD_NO_LEADER (a silent drop, :1459-1462), otherwise FORWARDED.
+ *        TRANSFER_LEADER: no lead gives NO_LEADER (:1446-1449); with a lead
+ *        and term == 0 FORWARDED; with a lead and a nonzero term
+ *        QE_QD_REF_PANIC: the reference's send panics on a set term
+ *        (:407-409); the record is not forwarded and is counted in
+ *        QE_STAT_INVARIANT_VIOLATIONS.  READ_INDEX_RESP: QE_QD_READ_STATE
+ *        (:1465-1470; a record has exactly one key, so the len(Entries) != 1
+ *        check has no counterpart).
+ *  4. Order within a group.  The records of a group are handled in list order
+ *     until the first ROUTED or STEPDOWN record.  That record closes the
+ *     group: every later record of the group that is not BAD gets
+ *     QE_QD_DEFERRED.  So a group gets at most one row-writing record per pass
+ *     and the relative order of, say, a transfer and a proposal is kept
+ *     exactly; the records before the closer write no state, so any number of
+ *     them is handled in one pass.
+ *  5. Output list: dense, ascending in list position, one record for each
+ *     FORWARDED, READ_STATE (a STEPDOWN READ_INDEX_RESP's included) and
+ *     PROP_DROPPED record.  group; kind = QE_QO_FWD / _READ_STATE /
+ *     _PROP_DROPPED; type = the input type; to = the lead slot for FWD, else
+ *     0xFF; from = for FWD the record's from where it is a slot, else
+ *     self_slot[g] (send fills From only when it is None, :387-389; a forwarded
+ *     From is kept), else 0xFF; term = f->term[g] for a forwarded
+ *     TRANSFER_LEADER, else 0 (PROP and READ_INDEX go without a term); index =
+ *     the record's index for READ_STATE, else 0; key; src = the list position.
+ *     *count is the full number of records; nothing at or past min(*count,
+ *     capacity) is touched in any output array (qe_outbox rule 3).  A FWD
+ *     TRANSFER_LEADER record has type 10 and carries its term: the receiving
+ *     host may hand it to qe_inbox or to this call as it is.
+ *  6. Rows.  p_num_entries, ri_request, v_type [G] and r_type (columns < G of
+ *     each of the S slot rows; the pad columns are not touched) are COMPLETE: 0
+ *     where nothing was routed.  Every other row is written only where its
+ *     complete row is non-zero.  p_src / ri_src / v_src [G] and r_src
+ *     [S][stride] (each optional) get the list position of the routed record.
+ *     disposition[i] = QE_QD_* of every record.  deferred[0 .. *deferred_count)
+ *     = the positions of the DEFERRED records, ascending; the next pass's list
+ *     is those records followed by what arrived since.
+ *  7. Consequences.  A request pass is a pass of its own: its rows are not
+ *     merged with qe_inbox's rows of the same round.  In the order a host
+ *     calls the steps on them the rows feed qe_propose, qe_read_index
+ *     (ri_request, ri_key), qe_read_note (from = ri_from), qe_progress_step,
+ *     qe_vote_step and qe_read_states (ri_*).  Because of rule 4 no two of
+ *     these touch the same group.
+ *  8. stats (optional): QE_STAT_GROUPS += groups with a ROUTED record;
+ *     QE_STAT_REQ_* += records by disposition, BAD and REF_PANIC also into
+ *     QE_STAT_INVARIANT_VIOLATIONS; QE_STAT_CHECKSUM += mix64(mix64(group *
+ *     0x9E3779B97F4A7C15 ^ 0xA24BAED4963EE407 ^ disposition << 56 ^ type << 48 ^
+ *     from << 40) ^ i) per list record.
+ * Every array is a DEVICE pointer; scratch is qe_requests_scratch_bytes(G,
+ * num_records) bytes of device memory, 8-B aligned: 4 * G + 2 * n bytes plus 2 *
+ * qe_collect_scratch_bytes(n) -- one word per group (qe_inbox: 3 + S), two flag
+ * bytes per record and qe_collect's part for each of the two lists.
+ * Stream-ordered, no host synchronisation: an init pass over the groups, two
+ * passes over the records, and per list qe_collect's count and scan and a fill
+ * of the record-list layer.  Positions are keys of 32-bit atomicMin, which is
+ * order-free: the outputs are bit-exact from run to run.
+ * QE_ERANGE: num_records > 0xFFFFFFF0.
+ * QE_EINVAL: a NULL p / f / in / out; f->term, f->state or f->lead NULL;
+ * p->self_slot NULL; num_slots outside 1..16 or a nonzero reserved field of p;
+ * in->reserved nonzero; a bit of in->flags other than QE_REQ_NO_FORWARD; stride
+ * < num_groups; max_cc > QE_PROP_MAX_CC; max_cc > 0 with cc_stride < num_groups
+ * or a NULL p_cc_count / p_cc_pos / p_cc_leave / p_cc_size, or with in->cc_count
+ * and a NULL in->cc_pos / cc_leave / cc_size; num_records > 0 with a NULL group /
+ * type / from / term / index / key (num_entries, payload and cc_count may be
+ * NULL: zeros, none); a NULL p_num_entries / ri_request / ri_key / ri_from /
+ * v_type / v_from / v_term / v_index / v_log_term / r_type / disposition /
+ * deferred / deferred_count / count; capacity > 0 with a NULL array of the
+ * output list; scratch NULL (with num_groups > 0) or not 8-B aligned.  Every
+ * argument check runs before the first HIP call.  num_records == 0 is QE_OK
+ * with complete rows and both counts 0; num_groups == 0 is QE_OK with both
+ * counts 0 and nothing else written. */
+#define QE_QMSG_TRANSFER_LEADER 10    /* MsgTransferLeader (= QE_IMSG_TRANSFER_LEADER) */
+#define QE_QMSG_PROP 17               /* MsgProp          */
+#define QE_QMSG_READ_INDEX 18         /* MsgReadIndex     */
+#define QE_QMSG_READ_INDEX_RESP 19    /* MsgReadIndexResp */
+#define QE_QD_ROUTED 1            /* in this pass's rows (= QE_ID_ROUTED)      */
+#define QE_QD_STEPDOWN 2          /* a higher term, as a vote row              */
+#define QE_QD_DEFERRED 3          /* waits for the next pass                   */
+#define QE_QD_DROP_LOWER_TERM 4
+#define QE_QD_NO_ARM 5            /* the receiver's step function ignores it   */
+#define QE_QD_FORWARDED 6         /* to the lead: a QE_QO_FWD record           */
+#define QE_QD_READ_STATE 7        /* a QE_QO_READ_STATE record                 */
+#define QE_QD_PROP_DROPPED 8      /* ErrProposalDropped: a QE_QO_PROP_DROPPED record */
+#define QE_QD_NO_LEADER 9         /* a follower without a lead drops it silently */
+#define QE_QD_REF_PANIC 10        /* the reference would panic; nothing is sent */
+#define QE_QD_BAD 255
+#define QE_QO_FWD 1               /* the request, addressed to the lead        */
+#define QE_QO_READ_STATE 2        /* ReadState{Index: index, RequestCtx: key}  */
+#define QE_QO_PROP_DROPPED 3      /* ErrProposalDropped for the caller         */
+#define QE_REQ_NO_FORWARD 1u      /* Config.DisableProposalForwarding, batch-wide */
+#define QE_STAT_REQ_BAD QE_STAT_COMMIT_INF              /* qe_requests: records by disposition */
+#define QE_STAT_REQ_NO_ARM QE_STAT_COMMIT_SUM
+#define QE_STAT_REQ_NO_LEADER QE_STAT_COMMIT_ZERO
+#define QE_STAT_REQ_ROUTED QE_STAT_VOTE_WON
+#define QE_STAT_REQ_LOWER_TERM QE_STAT_VOTE_LOST
+#define QE_STAT_REQ_DEFERRED QE_STAT_VOTE_PENDING
+#define QE_STAT_REQ_FORWARDED QE_STAT_GRANTED
+#define QE_STAT_REQ_PROP_DROPPED QE_STAT_REJECTED
+#define QE_STAT_REQ_READ_STATE QE_STAT_COMMIT_ADVANCED
+#define QE_STAT_REQ_REF_PANIC QE_STAT_READ_RELEASED
+#define QE_STAT_REQ_STEPDOWN QE_STAT_STEPDOWNS
+
+typedef struct qe_requests_in {
+  uint64_t num_records;         /* n <= 0xFFFFFFF0 */
+  uint32_t max_cc;              /* conf-change rows per record, <= QE_PROP_MAX_CC */
+  uint32_t flags;               /* QE_REQ_NO_FORWARD or 0 */
+  const uint64_t *group;        /* [n] the RECEIVER's global group id */
+  const uint8_t  *type, *from;  /* [n] QE_QMSG_*; a slot in the receiver's numbering or 0xFF */
+  const uint64_t *term;         /* [n] 0 = local, or forwarded without a term */
+  const uint64_t *index;        /* [n] m.Index of a READ_INDEX_RESP */
+  const uint64_t *key;          /* [n] the request key of a READ_INDEX / READ_INDEX_RESP */
+  const uint32_t *num_entries;  /* [n] or NULL (zeros): len(m.Entries) of a PROP */
+  const uint64_t *payload;      /* [n] or NULL (zeros): qe_proposals.payload */
+  const uint8_t  *cc_count;     /* [n] or NULL (none): qe_proposals.cc_count */
+  const uint32_t *cc_pos;       /* [max_cc][n] */
+  const uint8_t  *cc_leave;     /* [max_cc][n] */
+  const uint32_t *cc_size;      /* [max_cc][n] */
+  uint64_t reserved;            /* must be 0 */
+} qe_requests_in;
+
+typedef struct qe_requests_out {
+  uint32_t *p_num_entries;      /* [G] qe_proposals; complete */
+  uint64_t *p_payload;          /* [G] or NULL */
+  uint8_t  *p_cc_count;         /* [G]; may be NULL with max_cc 0 */
+  uint32_t *p_cc_pos;           /* [max_cc][cc_stride] */
+  uint8_t  *p_cc_leave;         /* [max_cc][cc_stride] */
+  uint32_t *p_cc_size;          /* [max_cc][cc_stride] */
+  uint64_t cc_stride;           /* >= num_groups (read with max_cc > 0) */
+  uint8_t  *ri_request;         /* [G] qe_read_index's request row; complete */
+  uint64_t *ri_key;             /* [G] qe_read_index's key row */
+  uint8_t  *ri_from;            /* [G] qe_read_note's / qe_read_states' from row */
+  uint8_t  *v_type, *v_from;    /* [G] qe_vote_msgs; v_type complete */
+  uint64_t *v_term, *v_index, *v_log_term;
+  uint8_t  *v_flags;            /* [G] or NULL */
+  uint8_t  *r_type;             /* [S][stride] qe_peer_msgs.type; complete in the columns < G */
+  uint32_t *p_src, *ri_src, *v_src;  /* [G], each or NULL */
+  uint32_t *r_src;              /* [S][stride] or NULL */
+  uint8_t  *disposition;        /* [n] QE_QD_* */
+  uint32_t *deferred;           /* [n] positions of the DEFERRED records, ascending */
+  uint64_t *deferred_count;     /* device */
+  uint64_t capacity;            /* of the output list */
+  uint64_t *group;              /* [capacity] */
+  uint8_t  *kind, *type;        /* [capacity] QE_QO_*, QE_QMSG_* */
+  uint8_t  *to, *from;          /* [capacity] slots, 0xFF = none */
+  uint64_t *term, *index, *key; /* [capacity] */
+  uint32_t *src;                /* [capacity] the record's list position */
+  uint64_t *count;              /* device: the full number, may exceed capacity */
+} qe_requests_out;
+
+size_t qe_requests_scratch_bytes(uint64_t num_groups, uint64_t num_records);
+int qe_requests(const qe_progress *p, const qe_follower *f, const qe_requests_in *in,
+                const qe_requests_out *out, void *scratch, uint64_t *stats, void *stream);
+
 /* ---- statistics -------------------------------------------------------- */
 
 /* out[QE_STATS_COUNTERS] (device) = sum over shards of stats (device). */

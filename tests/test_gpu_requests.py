@@ -1,0 +1,331 @@
+"""qe_requests on the device against tests/requests_model.py on random lists:
+every row of the four families, the source positions, the dispositions, the
+deferred list, the output list with its count and the statistics.  Every output
+is prefilled with a sentinel and whatever the rules do not write must keep it;
+the resident rows must be byte-identical before and after; the same list
+handled twice must give identical bytes.
+
+The shapes: n = 0, 1, 63, 64, 65 (the record tile's edges), 4095, 4096, 4097
+(the chunk's edges) and 3 * 4096 + 17; G = 1 (one lane), 64, 67 (a ragged second
+tile) and 4099 (a second 4096-chunk of the init pass) with stride = G + 3; S = 1,
+3, 5, 16; group_offset 0 and 2^33; max_cc 0, 2, 8; all four types and types that
+are none; all four states; lead set, None (0xFF) and out of range (S); receiver
+terms 3..6 against message terms one below, equal, one above and 0; records
+outside the batch on both sides, bad slots, empty proposals, proposals with a
+term and transfers without a transferee; capacity 0, count - 1, count and
+more."""
+import zlib
+from collections import Counter
+
+import numpy as np
+import pytest
+import torch
+
+from tests import requests_model as qm
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+SENT = 0x0E
+GOFF = 1 << 33
+NP = {torch.int64: np.uint64, torch.int32: np.uint32, torch.int16: np.uint16, torch.uint8: np.uint8}
+TYPES = [qm.TRANSFER_LEADER, qm.PROP, qm.READ_INDEX, qm.READ_INDEX_RESP, 0, 9, 11, 16, 20, 255]
+TYPE_P = np.array([6, 8, 8, 6, .3, .3, .3, .3, .3, .3])
+
+
+@pytest.fixture(scope="module")
+def eng():
+    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    from etcd_amd import engine
+    return engine
+
+
+def host(t):
+    return t.cpu().numpy().view(NP[t.dtype])
+
+
+def sentinel(t):
+    if t is not None:
+        t.view(torch.uint8).fill_(SENT)
+
+
+def kept(a):
+    """Every byte of `a` is still the sentinel's."""
+    return bool((np.ascontiguousarray(a).view(np.uint8) == SENT).all())
+
+
+def random_state(rng, G, S):
+    return dict(term=rng.integers(3, 7, G).astype(np.uint64),
+                state=rng.choice([0, 0, 1, 2, 2, 3], G).astype(np.uint8),
+                lead=rng.choice([0, S - 1, S - 1, 0xFF, S], G).astype(np.uint8),
+                self_slot=rng.integers(0, S, G).astype(np.uint8))
+
+
+def random_list(rng, G, S, max_cc, n, goff, rterm, mode="rand"):
+    groups = np.array([0, G - 1]) if mode == "two" else np.arange(G)
+    recs = []
+    for i in range(n):
+        g = int(rng.choice(groups))
+        base = int(rterm[g])
+        gid = goff + g
+        u = rng.random()
+        if u < 0.02 and goff:
+            gid = goff - 1 - int(rng.integers(0, 3))      # below the batch
+        elif u < 0.04:
+            gid = goff + G + int(rng.integers(0, 3))      # above it
+        t = int(rng.choice(TYPES, p=TYPE_P / TYPE_P.sum()))
+        frm = int(rng.choice([int(rng.integers(0, S)), int(rng.integers(0, S)), qm.NONE, S, 200],
+                             p=[.45, .25, .25, .025, .025]))
+        if t in (qm.PROP, qm.READ_INDEX):
+            term = 0 if rng.random() < 0.95 else base
+        else:
+            term = base + int(rng.choice([-1, 0, 0, 0, 1, -base, -base]))
+        ne = int(rng.choice([0, 1, 1, 2, 7], p=[.06, .4, .24, .2, .1]))
+        cc = [(int(rng.integers(0, 8)), int(rng.integers(0, 2)), int(rng.integers(0, 1 << 20)))
+              for _ in range(int(rng.choice([0, 0, 1, max_cc, max_cc + 1])))]
+        recs.append(qm.rec(gid, t, frm, term, int(rng.integers(0, 1 << 62)),
+                           int(rng.integers(0, 1 << 63)) * 2 + 1, ne, int(rng.integers(0, 1 << 40)),
+                           cc))
+    return recs
+
+
+def arrays(recs, max_cc):
+    a = {k: np.array([m[k] for m in recs], np.uint64)
+         for k in ("group", "term", "index", "key", "payload")}
+    a["type"] = np.array([m["type"] for m in recs], np.uint8)
+    a["from"] = np.array([m["from"] for m in recs], np.uint8)
+    a["num_entries"] = np.array([m["num_entries"] for m in recs], np.uint32)
+    a["cc_count"] = np.array([len(m["cc"]) for m in recs], np.uint8)
+    if max_cc:
+        cc = [[(m["cc"] + [(0, 0, 0)] * max_cc)[k] for m in recs] for k in range(max_cc)]
+        cc = np.array(cc, np.uint64).reshape(max_cc, len(recs), 3)
+        a["cc_pos"] = cc[:, :, 0].astype(np.uint32)
+        a["cc_leave"] = cc[:, :, 1].astype(np.uint8)
+        a["cc_size"] = cc[:, :, 2].astype(np.uint32)
+    return a
+
+
+class Pass:
+    """Fresh, sentinel-filled rows and lists, and one handled pass."""
+
+    def __init__(self, e, ps, fol, recs, max_cc, cap, src=True, flags=True, no_forward=False,
+                 stats=True):
+        n = len(recs)
+        self.rq = rq = e.Requests(ps, n + 5, capacity=cap, max_cc=max_cc, src=src)
+        if n:
+            rq.load_host(**arrays(recs, max_cc))
+        self.props = e.Proposals(ps, max_cc=max_cc)
+        self.pm, self.vm = e.PeerMsgs(ps, outputs=False), e.VoteMsgs(ps)
+        if not flags:
+            self.vm.flags = None
+        pr, vm = self.props, self.vm
+        self.p = dict(num_entries=pr.num_entries, payload=pr.payload, cc_count=pr.cc_count)
+        self.cc = dict(pos=pr.cc_pos, leave=pr.cc_leave, size=pr.cc_size)
+        self.ri = dict(request=rq.ri_request, key=rq.ri_key, frm=rq.ri_from)
+        self.v = dict(type=vm.type, frm=vm.from_, term=vm.term, index=vm.index,
+                      log_term=vm.log_term, flags=vm.flags)
+        self.untouched = [self.pm.index, self.pm.reject_hint, self.pm.log_term]
+        self.list = {k: getattr(rq, k) for k in rq.ARRAYS if k != "count"}
+        self.all = ([t for d in (self.p, self.cc, self.ri, self.v, self.list) for t in d.values()
+                     if t is not None] + self.untouched +
+                    [t for t in (self.pm.type, rq.p_src, rq.ri_src, rq.v_src, rq.r_src,
+                                 rq.disposition, rq.deferred_pos, rq.deferred_count, rq.count)
+                     if t is not None])
+        for t in self.all:
+            sentinel(t)
+        self.stats = e.stats_buffer(DEV) if stats else None
+        e.requests(ps, fol, rq, self.props, self.pm, self.vm, stats=self.stats,
+                   no_forward=no_forward)
+        self.folded = host(e.stats_reduce(self.stats)) if stats else None
+        torch.cuda.synchronize()
+
+    def snapshot(self):
+        out = [t.clone() for t in self.all]
+        return out + ([torch.from_numpy(self.folded.copy())] if self.folded is not None else [])
+
+
+def check_family(name, complete, rows, want, src, G, opt=()):
+    """rows: field -> tensor [G]; want: g -> the model's row; `complete` names
+    the family's complete row and gives its value per model row."""
+    key, value = complete
+    has = np.zeros(G, bool)
+    has[list(want)] = True
+    np.testing.assert_array_equal(
+        host(rows[key])[:G], [value(want[g]) if g in want else 0 for g in range(G)],
+        err_msg=f"{name}_{key}")
+    for k, t in dict(rows, src=src).items():
+        if k == key or t is None:
+            assert k == key or k in opt + ("src",), (name, k)
+            continue
+        got = host(t)[:G]
+        exp = np.array([want[g][k] for g in sorted(want)], np.uint64).astype(got.dtype)
+        np.testing.assert_array_equal(got[has], exp, err_msg=f"{name}_{k}")
+        assert kept(got[~has]), f"{name}_{k}: written where {name}_{key} is 0"
+
+
+def setup(e, G, S, goff, st):
+    ps = e.ProgressState(G, S, 1, 1, DEV, group_offset=goff, stride=G + 3, extras=("self_slot",))
+    ps.load_host(self_slot=st["self_slot"])
+    fol = e.Follower(ps)
+    fol.load_host(term=st["term"], state=st["state"], lead=st["lead"])
+    return ps, fol
+
+
+def model_state(G, S, goff, st):
+    return qm.state(num_groups=G, group_offset=goff, num_slots=S, **st)
+
+
+def run_and_check(e, G, S, max_cc, goff, st, recs, cap="full", src=True, flags=True,
+                  no_forward=False):
+    """One list on the device, twice, against the sequential model -> (the
+    model's output, the second Pass)."""
+    n, stride = len(recs), G + 3
+    want = qm.route(model_state(G, S, goff, st), recs, no_forward=no_forward, max_cc=max_cc)
+    count = len(want.records)
+    cap = {"full": n + 5, "zero": 0, "minus1": max(0, count - 1), "exact": count}[cap]
+    ps, fol = setup(e, G, S, goff, st)
+    resident = [fol.term, fol.state, fol.lead, ps.self_slot]
+    before = [t.clone() for t in resident]
+    runs = []
+    for _ in range(2):
+        ps_ = Pass(e, ps, fol, recs, max_cc, cap, src, flags, no_forward)
+        runs.append(ps_.snapshot())
+    for x, y in zip(*runs):
+        assert torch.equal(x, y), "two runs of one list differ"
+    for x, y in zip(resident, before):
+        assert torch.equal(x, y), "a resident row was written"
+    rq = ps_.rq
+    s = lambda k: getattr(rq, k) if src else None  # noqa: E731
+    # ---- the per-group families ----
+    check_family("p", ("num_entries", lambda r: r["num_entries"]), ps_.p, want.p, s("p_src"), G)
+    check_family("ri", ("request", lambda r: 1), ps_.ri, want.ri, s("ri_src"), G)
+    check_family("v", ("type", lambda r: r["type"]), ps_.v, want.v, s("v_src"), G, opt=("flags",))
+    for j, k in enumerate(("pos", "leave", "size")):
+        got = host(ps_.cc[k]).reshape(max(1, max_cc), G)
+        has = np.zeros(G, bool)
+        for g, r in want.p.items():
+            has[g] = True
+            np.testing.assert_array_equal(got[:max_cc, g], [c[j] for c in r["cc"]],
+                                          err_msg=f"p_cc_{k}")
+        assert kept(got[:, ~has]) and kept(got[max_cc:]), f"p_cc_{k} written for no proposal"
+    # ---- the transfer rows [S][stride] ----
+    rt = host(ps_.pm.type).reshape(S, stride)
+    exp = np.zeros((S, G), np.uint8)
+    for (sl, g), r in want.r.items():
+        exp[sl, g] = r["type"]
+    np.testing.assert_array_equal(rt[:, :G], exp, err_msg="r_type")
+    assert kept(rt[:, G:]), "r_type: a pad column was written"
+    if src:
+        got = host(rq.r_src).reshape(S, stride)
+        has = np.zeros((S, stride), bool)
+        for (sl, g), r in want.r.items():
+            has[sl, g] = True
+            assert int(got[sl, g]) == r["src"]
+        assert kept(got[~has])
+    for t in ps_.untouched:
+        assert kept(host(t)), "a peer row the call does not own was written"
+    # ---- per record ----
+    disp = host(rq.disposition)
+    np.testing.assert_array_equal(disp[:n], want.disposition, err_msg="disposition")
+    assert kept(disp[n:])
+    dcount = int(host(rq.deferred_count)[0])
+    assert dcount == len(want.deferred)
+    dl = host(rq.deferred_pos)
+    np.testing.assert_array_equal(dl[:dcount], want.deferred, err_msg="deferred")
+    assert kept(dl[dcount:])
+    np.testing.assert_array_equal(rq.deferred, want.deferred)
+    # ---- the output list ----
+    assert int(host(rq.count)[0]) == count
+    m = min(count, cap)
+    got_count, got = rq.records()
+    assert got_count == count
+    for k, t in ps_.list.items():
+        full = host(t)
+        exp = np.array([r["frm" if k == "from_" else k] for r in want.records[:m]], np.uint64)
+        np.testing.assert_array_equal(full[:m], exp.astype(full.dtype), err_msg="list " + k)
+        np.testing.assert_array_equal(got[k], full[:m])
+        assert kept(full[m:]), f"list {k}: written at or past min(count, capacity)"
+    for i in range(16):
+        assert int(ps_.folded[i]) == want.stats.get(i, 0), ("stat", i)
+    return want, ps_
+
+
+#        G     S   cc n              goff  options
+CASES = [
+    (1,    1,  0, 0,             0,    {}),
+    (1,    3,  2, 1,             GOFF, {}),
+    (1,    5,  2, 4097,          0,    {}),
+    (64,   5,  8, 63,            0,    dict(cap="exact")),
+    (64,   16, 0, 64,            GOFF, dict(src=False, flags=False)),
+    (64,   3,  2, 4096,          GOFF, dict(mode="two")),
+    (67,   3,  2, 65,            0,    dict(cap="minus1")),
+    (67,   1,  8, 4095,          GOFF, dict(cap="zero")),
+    (67,   5,  0, 4096,          0,    dict(no_forward=True)),
+    (67,   16, 2, 4097,          GOFF, dict(cap="minus1", src=False)),
+    (4099, 3,  8, 3 * 4096 + 17, 0,    {}),
+    (4099, 5,  2, 4097,          GOFF, dict(cap="exact", no_forward=True)),
+    (4099, 16, 0, 0,             GOFF, {}),
+    (4099, 1,  0, 64,            0,    dict(flags=False)),
+]
+
+
+@pytest.mark.parametrize("G,S,max_cc,n,goff,o", CASES)
+def test_requests_match_model(eng, G, S, max_cc, n, goff, o):
+    o = dict(o)
+    rng = np.random.default_rng(zlib.crc32(repr((G, S, max_cc, n, goff, sorted(o.items()))).encode()))
+    st = random_state(rng, G, S)
+    recs = random_list(rng, G, S, max_cc, n, goff, st["term"], o.pop("mode", "rand"))
+    want, _ = run_and_check(eng, G, S, max_cc, goff, st, recs, **o)
+    if n >= 4095 and G == 67:  # enough records per group: every outcome occurs
+        assert set(want.disposition) == set(qm.QD_NAMES), Counter(want.disposition)
+        assert {r["kind"] for r in want.records} == {1, 2, 3}
+
+
+def test_one_leader_group_routes_one_and_defers_the_rest_in_order(eng):
+    G, S, g, n = 67, 3, 41, 4097
+    st = dict(term=np.full(G, 4, np.uint64), state=np.full(G, qm.ST_LEADER, np.uint8),
+              lead=np.full(G, 1, np.uint8), self_slot=np.full(G, 1, np.uint8))
+    recs = [qm.rec(GOFF + g, qm.PROP, i % S, 0, 0, i, 1 + i % 5, i) for i in range(n)]
+    want, p = run_and_check(eng, G, S, 0, GOFF, st, recs)
+    assert want.disposition == [qm.ROUTED] + [qm.DEFERRED] * 4096
+    np.testing.assert_array_equal(p.rq.deferred, np.arange(1, n))
+    assert int(host(p.props.num_entries)[g]) == 1 and int(host(p.rq.p_src)[g]) == 0
+
+
+def test_one_follower_forwards_every_record_in_order(eng):
+    G, S, g, n = 67, 3, 66, 4097
+    st = dict(term=np.full(G, 4, np.uint64), state=np.full(G, qm.ST_FOLLOWER, np.uint8),
+              lead=np.full(G, 2, np.uint8), self_slot=np.full(G, 0, np.uint8))
+    recs = [qm.rec(g, (qm.PROP, qm.READ_INDEX, qm.TRANSFER_LEADER)[i % 3], 1 if i % 3 == 2 else
+                   (qm.NONE, 1)[i % 2], 0, 0, 1000 + i, 1) for i in range(n)]
+    want, p = run_and_check(eng, G, S, 0, 0, st, recs)
+    assert want.disposition == [qm.FORWARDED] * n
+    count, got = p.rq.records()
+    assert count == n and not len(p.rq.deferred)
+    np.testing.assert_array_equal(got["src"], np.arange(n))
+    np.testing.assert_array_equal(got["key"], 1000 + np.arange(n))
+    assert set(got["to"]) == {2} and set(got["from_"]) == {0, 1}
+    np.testing.assert_array_equal(got["term"], np.where(np.arange(n) % 3 == 2, 4, 0))
+
+
+def test_deferred_list_fed_back_until_empty_equals_the_model_run_to_the_end(eng):
+    e, G, S, max_cc, goff = eng, 64, 5, 2, GOFF
+    rng = np.random.default_rng(99)
+    st = random_state(rng, G, S)
+    recs = random_list(rng, G, S, max_cc, 700, goff, st["term"])
+    passes = qm.run_to_end(model_state(G, S, goff, st), recs, max_cc=max_cc)
+    assert len(passes) >= 4
+    ps, fol = setup(e, G, S, goff, st)
+    cur, got = recs, []
+    while cur:
+        p = Pass(e, ps, fol, cur, max_cc, len(cur), stats=False)
+        got.append((p.rq.dispositions().tolist(), p.rq.records()[1]["src"].tolist(),
+                    host(p.props.num_entries)[:G].tolist(), host(p.rq.ri_request)[:G].tolist()))
+        nxt = p.rq.deferred
+        assert len(nxt) < len(cur)  # every pass handles something: the loop ends
+        cur = [cur[i] for i in nxt]
+    assert len(got) == len(passes)
+    for (disp, srcs, ne, rr), w in zip(got, passes):
+        assert disp == w.disposition
+        assert srcs == [r["src"] for r in w.records]
+        assert ne == [w.p[g]["num_entries"] if g in w.p else 0 for g in range(G)]
+        assert rr == [int(g in w.ri) for g in range(G)]
