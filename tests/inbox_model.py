@@ -12,6 +12,10 @@ carries num_groups, group_offset, num_slots, stride and the rows term[G] and
 state[G] of qe_follower."""
 from types import SimpleNamespace
 
+import numpy as np
+
+from tests.tick_model import mix64 as mix64_np
+
 APP, SNAP, HEARTBEAT = 1, 2, 3
 APP_RESP, APP_RESP_REJECT, HEARTBEAT_RESP, SNAP_STATUS, SNAP_STATUS_REJECT = 4, 5, 6, 7, 8
 UNREACHABLE, TRANSFER_LEADER = 9, 10
@@ -40,6 +44,23 @@ def mix64(z):
     z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
     z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
     return z ^ (z >> 31)
+
+
+def record_hash(group, disp, type, frm, i):
+    """The STAT_CHECKSUM term of record i of the list."""
+    h = mix64((group * PHI) ^ SALT ^ (disp << 56) ^ (type << 48) ^ (frm << 40))
+    return mix64(h ^ i)
+
+
+def record_hashes(group, disp, type, frm, salt=SALT):
+    """record_hash over the arrays of a whole list (position = array index),
+    vectorised -> uint64[n]; tests/test_inbox_model.py pins it to the scalar
+    form.  `salt`: tests/requests_model.py hashes the same words under its own."""
+    u =lambda a: np.asarray(a).astype(np.uint64)  # noqa: E731
+    with np.errstate(over="ignore"):
+        h = mix64_np((u(group) * np.uint64(PHI)) ^ np.uint64(salt) ^ (u(disp) << np.uint64(56)) ^
+                     (u(type) << np.uint64(48)) ^ (u(frm) << np.uint64(40)))
+    return mix64_np(h ^ np.arange(len(h), dtype=np.uint64))
 
 
 def cls_of(t):
@@ -150,8 +171,7 @@ def route(st, recs, tick_action=None, msg_runs=4, same_from_joins=False):
     for i, m in enumerate(recs):
         stats[BY_DISPOSITION[disp[i]]] += 1
         stats[STAT_VIOLATIONS] += disp[i] == BAD
-        h = mix64((m["group"] * PHI) ^ SALT ^ (disp[i] << 56) ^ (m["type"] << 48) ^
-                  (m["from"] << 40))
-        stats[STAT_CHECKSUM] = (stats[STAT_CHECKSUM] + mix64(h ^ i)) & M64
+        h = record_hash(m["group"], disp[i], m["type"], m["from"], i)
+        stats[STAT_CHECKSUM] = (stats[STAT_CHECKSUM] + h) & M64
     out.stats = stats
     return out

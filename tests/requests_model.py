@@ -11,6 +11,8 @@ or NONE), term, index, key, num_entries, payload, cc [(pos, leave, size), ...].
 lead[G] of qe_follower and self_slot[G] of qe_progress."""
 from types import SimpleNamespace
 
+from tests.inbox_model import record_hashes as inbox_hashes
+
 TRANSFER_LEADER, PROP, READ_INDEX, READ_INDEX_RESP = 10, 17, 18, 19
 TYPES = (TRANSFER_LEADER, PROP, READ_INDEX, READ_INDEX_RESP)
 NONE = 0xFF
@@ -35,6 +37,19 @@ def mix64(z):
     z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
     z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
     return z ^ (z >> 31)
+
+
+def record_hash(group, disp, type, frm, i):
+    """The STAT_CHECKSUM term of record i of the list."""
+    h = mix64((group * PHI) ^ SALT ^ (disp << 56) ^ (type << 48) ^ (frm << 40))
+    return mix64(h ^ i)
+
+
+def record_hashes(group, disp, type, frm):
+    """record_hash over the arrays of a whole list (position = array index),
+    vectorised -> uint64[n]; tests/test_requests_model.py pins it to the scalar
+    form."""
+    return inbox_hashes(group, disp, type, frm, SALT)
 
 
 def rec(group, type, frm=NONE, term=0, index=0, key=0, num_entries=0, payload=0, cc=()):
@@ -129,9 +144,8 @@ def _finish(st, recs, disp, kinds, max_cc, fwd_from_self=False):
     for i, m in enumerate(recs):
         stats[BY_DISPOSITION[disp[i]]] += 1
         stats[STAT_VIOLATIONS] += disp[i] in (BAD, REF_PANIC)
-        h = mix64((m["group"] * PHI) ^ SALT ^ (disp[i] << 56) ^ (m["type"] << 48) ^
-                  (m["from"] << 40))
-        stats[STAT_CHECKSUM] = (stats[STAT_CHECKSUM] + mix64(h ^ i)) & M64
+        h = record_hash(m["group"], disp[i], m["type"], m["from"], i)
+        stats[STAT_CHECKSUM] = (stats[STAT_CHECKSUM] + h) & M64
     out.stats = stats
     return out
 

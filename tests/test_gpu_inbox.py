@@ -12,7 +12,11 @@ The shapes: G = 1 (one lane), 63 (a ragged tile), 65 (a ragged second tile) and
 4096 records aimed at two groups (every atomic of a tile on two words); records
 outside the batch on both sides; with and without tick_action, ctx, flags and
 the *_src rows; receiver terms 3..6 against message terms one below, equal, one
-above and 0, and every state, so that all five preamble outcomes occur."""
+above and 0, and every state, so that all five preamble outcomes occur.
+
+test_route_waves_walk is the one list long enough for the routing pass's capped
+grid (with statistics, 8 blocks per CU): its waves walk two and three tiles and
+carry their counters across them."""
 import zlib
 from collections import Counter
 
@@ -271,3 +275,79 @@ def test_inbox_matches_model(eng, G, S, E, n, mode, o):
         t = getattr(nxt, "from_" if k == "from" else k)
         np.testing.assert_array_equal(host(t)[: v.size], v.reshape(-1), err_msg="gathered " + k)
 
+
+
+def test_route_waves_walk(eng):
+    """A list of (2 * cap + 2) tiles and 21 records, cap = the wave count of
+    the routing pass's capped grid: with statistics every wave of k_inbox_p3
+    walks two tiles, two walk three and the last tile is ragged.  The same list
+    without statistics takes a wave per tile (what the model tests pin at small
+    n).  Between the two calls every row, source position, disposition and the
+    deferred list must be the same bytes, and the folded counters, carried by
+    each wave over its walk, must be what the outputs determine: the
+    per-disposition counters from the disposition array, QE_STAT_GROUPS the
+    distinct groups with a ROUTED record, QE_STAT_CHECKSUM the sum of
+    tests/inbox_model.py's record hash (record_hashes, pinned to the scalar one
+    in tests/test_inbox_model.py).  The records are generated on the device:
+    about two per group, 4% outside the batch, types that are none and slots
+    out of range, terms one below, equal, one above and 0."""
+    from tests import walk
+    from tests.test_gpu_outbox import DeviceRandom
+    e = eng
+    cus = torch.cuda.get_device_properties(DEV).multi_processor_count
+    n = walk.walk_groups(cus)
+    G, S, E = n // 2 + 3, 5, 1
+    o = dict(ALL, tick=False)
+    ps = e.ProgressState(G, S, 1, 1, DEV, group_offset=GOFF, stride=G + 3)
+    fol = e.Follower(ps)
+    per_group, rnd = DeviceRandom(G, 0x1B0C), DeviceRandom(n, 0x1B0D)
+    fol.term.copy_(per_group.ints(3, 7))
+    fol.state.copy_(torch.tensor([0, 1, 2, 2, 2, 3], dtype=torch.uint8, device=DEV)[per_group.ints(0, 6)])
+    g = rnd.ints(0, G)
+    u = torch.rand(n, generator=rnd.gen, device=DEV)
+    inside = (u >= 0.04)
+    gid = torch.where(inside, GOFF + g, torch.where(u < 0.02, GOFF - 1 - rnd.ints(0, 3),
+                                                    GOFF + G + rnd.ints(0, 3)))
+    base = torch.where(inside, fol.term[g], torch.full_like(g, 4))
+    delta = torch.tensor([-1, 0, 0, 0, 1], device=DEV)[rnd.ints(0, 5)]
+    term = torch.where(rnd.hit(1 / 6), torch.zeros_like(base), base + delta)
+    p = torch.tensor(TYPE_P, dtype=torch.float32, device=DEV)
+    ty = torch.multinomial(p, n, replacement=True, generator=rnd.gen).to(torch.uint8)
+    frm = torch.where(rnd.hit(0.02), torch.full_like(g, S), rnd.ints(0, S)).to(torch.uint8)
+    big = lambda: rnd.ints(0, 1 << 62)  # noqa: E731
+    rec = dict(group=gid, from_=frm, type=ty, term=term, index=big(), log_term=big(),
+               commit=big(), hint=big(), ctx=rnd.ints(0, 1 << 31, torch.int32),
+               flags=rnd.ints(0, 4, torch.uint8), ent_len=rnd.ints(0, 9, torch.int32),
+               ent_term=rnd.ints(1, 1 << 40))  # (E = 1: the run rows are [1][n])
+    runs = []
+    for stats in (None, e.stats_buffer(DEV)):
+        ib = e.Inbox(ps, n, E, ctx=o["ctx"], flags=o["flags"], src=o["src"])
+        for k, t in rec.items():
+            getattr(ib, k).copy_(t)
+        ib.n = n
+        for t in (ib.disposition, ib.deferred, ib.deferred_count, ib.f_src, ib.s_src, ib.v_src,
+                  ib.r_src):
+            sentinel(t)
+        rows = Rows(e, ps, fol, E, o)
+        e.inbox(ps, fol, ib, rows.lm, rows.sm, rows.vm, rows.pm, stats=stats)
+        runs.append(rows.tensors(ib))
+    names = [k for d in "fsvr" for k, t in getattr(rows, d).items() if t is not None]
+    assert len(runs[0]) == len(runs[1]) > len(names)
+    for i, (x, y) in enumerate(zip(*runs)):
+        assert torch.equal(x, y), ("with and without statistics differ", i, names[i:i + 1])
+    # ---- the counters against the outputs ----
+    folded = host(e.stats_reduce(stats))
+    disp = host(ib.disposition)
+    cnt = np.bincount(disp, minlength=256)
+    assert all(cnt[d] > 0 for d in im.ID_NAMES), {im.ID_NAMES[d]: int(cnt[d]) for d in im.ID_NAMES}
+    assert int(cnt.sum()) == n == sum(int(cnt[d]) for d in im.ID_NAMES)
+    for d, stat in im.BY_DISPOSITION.items():
+        assert int(folded[stat]) == int(cnt[d]), ("stat", im.ID_NAMES[d])
+    assert int(folded[im.STAT_VIOLATIONS]) == int(cnt[im.BAD])
+    gh = host(gid)
+    assert int(folded[im.STAT_GROUPS]) == np.unique(gh[disp == im.ROUTED]).size
+    with np.errstate(over="ignore"):
+        csum = int(np.add.reduce(im.record_hashes(gh, disp, host(ty), host(frm))))
+    assert int(folded[im.STAT_CHECKSUM]) == csum
+    count = int(host(ib.deferred_count)[0])
+    np.testing.assert_array_equal(host(ib.deferred)[:count], np.flatnonzero(disp == im.DEFERRED))

@@ -274,18 +274,45 @@ def test_progress_rounds_ring16_match_oracle(eng, S, masks, extras, F):
     rounds_vs_oracle(eng, S, masks, extras, 3, F, ring16=True)
 
 
-def rounds_vs_oracle(eng, S, masks, extras, R, F, ring16):
+def widen(pb, G):
+    """The random batch `pb` repeated with its own period up to G groups: the
+    generators above loop over the groups in Python, so a batch of many tiles
+    is a small one tiled (the period, pb.G, is no multiple of 64: the tiles
+    differ)."""
+    assert pb.stride == pb.G and pb.read_ovf is None and pb.read_keys is None  # [rows][G] only
+    idx = np.arange(G) % pb.G
+    out = pb.copy()
+    out.G = out.stride = G
+    for k, v in pb.__dict__.items():
+        if isinstance(v, np.ndarray) and k != "_flag":
+            setattr(out, k, np.ascontiguousarray(v.reshape(-1, pb.G)[:, idx]).reshape(-1))
+    return out
+
+
+def outputs_host(msgs):
+    """Every output row of a PeerMsgs as numpy arrays."""
+    return {k: getattr(msgs, k).cpu().numpy()
+            for k in ("sent", "snap", "timeout_now", "bcast", "msg_count", "msg_index",
+                      "read_released", "term_commit", "term_commit_index")}
+
+
+def rounds_vs_oracle(eng, S, masks, extras, R, F, ring16, G=3001, rounds=6, trace=None):
+    """`rounds` rounds of the differential on G groups (above 3001: the 3001
+    repeated, widen()).  trace: a list that gets, per round, the state, every
+    output, the folded statistics and the byte count of the device, for a
+    caller that compares two launch plans (tests/test_gpu_tiles_per_wave.py)."""
     rng = np.random.default_rng(100 + S + 7 * len(extras) + 31 * R + F + 1000 * ring16)
-    G = 3001
-    pb = random_state(rng, G, S, F, R, masks, extras, max_ents=int(rng.integers(0, 4)))
+    pb = random_state(rng, min(G, 3001), S, F, R, masks, extras, max_ents=int(rng.integers(0, 4)))
     if ring16:
         ring16_state(rng, pb)
     reads = "lead_transferee" in extras  # the ReadIndex queue with the full extras
     if reads:
         random_queue(rng, pb)
+    if G > pb.G:
+        pb = widen(pb, G)
     ps = to_device(eng, pb, masks, extras + (("reads",) if reads else ()))
     md = orc.mask_dtype(S)
-    for rnd in range(6):
+    for rnd in range(rounds):
         mtype, mindex, mhint, mlogterm = random_msgs(rng, pb)
         msgs = load_msgs(eng, ps, mtype, mindex, mhint, mlogterm)
         ctx = None
@@ -303,6 +330,8 @@ def rounds_vs_oracle(eng, S, masks, extras, R, F, ring16):
             w = (r_o == 1) | q
             np.testing.assert_array_equal(i_g.cpu().numpy().view(np.uint64)[w], i_o[w])
             assert_same(ps, pb)
+            if trace is not None:
+                trace.append(("read_index", r_g.cpu().numpy(), ps.host()))
         stats = eng.stats_buffer(DEV)
         if rnd % 2:
             msgs.bytes_requested = torch.zeros(1, dtype=torch.int64, device=DEV)
@@ -314,6 +343,9 @@ def rounds_vs_oracle(eng, S, masks, extras, R, F, ring16):
         np.testing.assert_array_equal(got, o.stats)
         if rnd % 2:
             assert int(msgs.bytes_requested.item()) == int(o.bytes[0]), (rnd, S)
+        if trace is not None:
+            trace.append(("step", rnd, ps.host(), outputs_host(msgs), got,
+                          int(msgs.bytes_requested.item()) if rnd % 2 else None))
         # a sendAppend / bcastAppend round to random peers
         want = rng.integers(0, 1 << S, G).astype(md)
         sei, me = int(rnd % 2), int(rng.integers(0, 5))

@@ -91,9 +91,17 @@ def test_propose_matches_oracle(eng, S, F, masks, extras, max_cc, max_ents, flag
     statistics and the algorithmic byte count equal the oracle's, over two
     launches in a row (flags 1: appendEntry alone); ring16: the rings in
     the 16-bit form (ABI 8)."""
+    propose_vs_oracle(eng, S, F, masks, extras, max_cc, max_ents, flags, ring16)
+
+
+def propose_vs_oracle(eng, S, F, masks, extras, max_cc, max_ents, flags, ring16, G=4099,
+                      trace=None):
+    """The differential of test_propose_matches_oracle on G groups.  trace: a
+    list that gets, per launch, the device's outputs, state and statistics or
+    byte count, for a caller that compares two launch plans
+    (tests/test_gpu_tiles_per_wave.py)."""
     from tests.test_gpu_progress import ring16_state
     rng = np.random.default_rng(7000 + 31 * S + F + flags + 500 * ring16)
-    G = 4099
     pb = random_state(rng, G, S, F, 3, masks, extras, max_ents=max_ents)
     if ring16:
         ring16_state(rng, pb)
@@ -128,6 +136,10 @@ def test_propose_matches_oracle(eng, S, F, masks, extras, max_cc, max_ents, flag
         else:
             got = eng.stats_reduce(st).cpu().numpy().view(np.uint64)
             np.testing.assert_array_equal(got, o.stats, err_msg="stats")
+        if trace is not None:
+            trace.append(([getattr(pr, k).cpu().numpy() for k in
+                           ("result", "cc_refused", "sent", "snap", "pending_conf_index",
+                            "uncommitted_size")], ps.host(), got_bytes if acct else got))
         res = o.result
         assert (res == 1).any() and (res == 0).any()
         if flags == 0 and "self_slot" in extras and S > 1:

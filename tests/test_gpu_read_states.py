@@ -468,3 +468,51 @@ def test_capacity_cuts(eng, capacity):
     rng = np.random.default_rng(7402)
     recs = run_extreme(eng, rng, 3 * 64 + 9, 5, capacity, capacity + 64, stats=capacity % 2 == 0)
     assert len(recs) == 395 and capacity < len(recs)
+
+
+def test_fill_blocks_walk(eng):
+    """test_fill_blocks_walk of tests/test_gpu_outbox.py for qe_read_states,
+    the one list whose tile holds runs of 0..257 records per group and loads
+    the book after stores: a quiet batch of one chunk more than the capped fill
+    grid has blocks, so that with statistics a block takes a second chunk.
+    About 1% of the groups release 1..3 reads (some forwarded: a
+    MsgReadIndexResp), a few have a TERM_COMMIT notice, a few an immediate
+    answer; read_cap 4.  The list of the call with statistics against the list
+    of the call without (a block per chunk, what the model tests pin), and the
+    per-kind counters against the kinds in the list."""
+    from tests.test_gpu_outbox import GOFF, DeviceRandom, same_list, walk_groups
+    e, L = eng, _lib
+    G, S, cap = walk_groups(), 2, 4
+    rnd = DeviceRandom(G, 0x0E5D)
+    t8, zero = torch.uint8, torch.zeros(G, dtype=torch.uint8, device=DEV)
+    ps = e.ProgressState(G, S, 1, 1, DEV, group_offset=GOFF,
+                         extras=("self_slot", "reads", "read_keys"), read_cap=cap)
+    ps.read_head.copy_(rnd.ints(300, 1 << 31, torch.int32))
+    ps.self_slot.copy_(rnd.ints(0, S + 1, t8))
+    ps.read_keys.copy_(torch.randint(0, 1 << 62, (G * cap,), generator=rnd.gen, device=DEV))
+    book = e.ReadBook(ps)
+    book.req_index.copy_(torch.randint(1, 1 << 40, (G * cap,), generator=rnd.gen, device=DEV))
+    book.req_from.copy_(torch.randint(0, S + 2, (G * cap,), generator=rnd.gen, device=DEV).to(t8))
+    rel = torch.where(rnd.hit(0.01), rnd.ints(1, 4, t8), zero)
+    msgs = SimpleNamespace(read_released=rel, term_commit=rnd.hit(0.002).to(t8),
+                           term_commit_index=rnd.ints(1, 1 << 40))
+    res = torch.where(rnd.hit(0.003), torch.full_like(zero, L.QE_RI_RESPOND),
+                      torch.where(rnd.hit(0.01), torch.full_like(zero, L.QE_RI_QUEUED), zero))
+    ri = (res, None, rnd.ints(1, 1 << 40), rnd.ints(0, S + 2, t8), rnd.ints(0, 1 << 62))
+    want = int((rel.sum() + msgs.term_commit.sum() + (res == L.QE_RI_RESPOND).sum()).item())
+    lists = []
+    for stats in (None, e.stats_buffer(DEV)):
+        rs = e.ReadStates(ps, want + 5)
+        e.read_states(ps, book, rs, msgs=msgs, ri=ri, stats=stats)
+        lists.append(rs)
+    n = same_list(lists[0], lists[1], (), 0)
+    assert n == want
+    folded = e.stats_reduce(stats)
+    kind = lists[0].kind[:n]
+    per_kind = {L.QE_STAT_READ_STATE: STATE, L.QE_STAT_READ_RESP: RESP,
+                L.QE_STAT_READ_TERM_COMMIT: TERM_COMMIT}
+    for stat, k in per_kind.items():
+        assert int(folded[stat].item()) == int((kind == k).sum().item()) > 0, ("stat", stat)
+    assert sum(int(folded[stat].item()) for stat in per_kind) == n  # the record count
+    groups = int(((rel != 0) | (msgs.term_commit != 0) | (res == L.QE_RI_RESPOND)).sum().item())
+    assert int(folded[0].item()) == groups  # QE_STAT_GROUPS: the groups with a record

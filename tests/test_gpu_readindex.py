@@ -12,7 +12,7 @@ import torch
 
 from oracle import orc
 from tests.test_gpu_progress import (DEV, EXTRAS, assert_outputs, assert_same, load_msgs,
-                                     random_msgs, random_state, to_device)
+                                     outputs_host, random_msgs, random_state, to_device)
 
 pytestmark = pytest.mark.gpu
 
@@ -73,6 +73,13 @@ def deep_ctx(rng, pb):
                                          (16, ("inc", "out"), 255)])
 @pytest.mark.parametrize("F", [8, 32])
 def test_deep_readindex_queues_match_oracle(eng, S, masks, cap, F):
+    deep_queues_vs_oracle(eng, S, masks, cap, F)
+
+
+def deep_queues_vs_oracle(eng, S, masks, cap, F, trace=None):
+    """trace: a list that gets the device's results, state, outputs and
+    statistics per call, for a caller that compares two launch plans
+    (tests/test_gpu_tiles_per_wave.py)."""
     rng = np.random.default_rng(9100 + 13 * S + cap + F)
     G = 3001
     pb = random_state(rng, G, S, F, 3, masks, EXTRAS, max_ents=1)
@@ -97,6 +104,8 @@ def test_deep_readindex_queues_match_oracle(eng, S, masks, cap, F):
             np.testing.assert_array_equal(i_g.cpu().numpy().view(np.uint64)[w], i_o[w])
             check_queue(ps, pb, f"read_index rnd {rnd}")
             assert (r_o == 5).any() and (r_o == 3).any()
+            if trace is not None:
+                trace.append((r_g.cpu().numpy(), ps.host()))
         mtype, mindex, mhint, mlogterm = random_msgs(rng, pb)
         hb = rng.random(mtype.size) < 0.6  # mostly heartbeat responses
         mtype[hb] = 3
@@ -116,6 +125,9 @@ def test_deep_readindex_queues_match_oracle(eng, S, masks, cap, F):
         if acct:
             assert int(msgs.bytes_requested.item()) == int(o.bytes[0]), rnd
         assert o.read_released.any()
+        if trace is not None:
+            trace.append((ps.host(), outputs_host(msgs), got,
+                          int(msgs.bytes_requested.item()) if acct else None))
         # MsgBeat: the newest pending context, however deep the queue
         commit, hctx, sent = eng.heartbeat(ps)
         _, o_ctx, o_sent = orc.heartbeat(pb)

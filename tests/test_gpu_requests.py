@@ -329,3 +329,102 @@ def test_deferred_list_fed_back_until_empty_equals_the_model_run_to_the_end(eng)
         assert srcs == [r["src"] for r in w.records]
         assert ne == [w.p[g]["num_entries"] if g in w.p else 0 for g in range(G)]
         assert rr == [int(g in w.ri) for g in range(G)]
+
+
+def test_route_waves_walk(eng):
+    """test_route_waves_walk of tests/test_gpu_inbox.py for k_requests_route: a
+    list of (2 * cap + 2) tiles and 21 records, cap = the wave count of the
+    routing pass's capped grid, so that with statistics every wave walks two
+    tiles, two walk three and the last tile is ragged; without statistics a
+    wave takes one tile (what the model tests pin at small n).  Between the two
+    calls every row, source position, disposition, the deferred list and the
+    output list must be the same bytes, and the folded counters, carried by
+    each wave over its walk, must be what the outputs determine (the checksum
+    through tests/requests_model.py's record_hashes, pinned to the scalar hash
+    in tests/test_requests_model.py).  Receivers in every state (leaders,
+    followers with and without a leader, candidates, pre-candidates), about two
+    records per group, generated on the device."""
+    from tests import walk
+    from tests.test_gpu_outbox import DeviceRandom
+    e = eng
+    cus = torch.cuda.get_device_properties(DEV).multi_processor_count
+    n = walk.walk_groups(cus)
+    G, S, max_cc = n // 2 + 3, 5, 2
+    u8, i32 = torch.uint8, torch.int32
+    pick = lambda rnd, vals, dt=torch.int64: torch.tensor(  # noqa: E731
+        vals, dtype=dt, device=DEV)[rnd.ints(0, len(vals))]
+    per_group, rnd = DeviceRandom(G, 0x2B0C), DeviceRandom(n, 0x2B0D)
+    ps = e.ProgressState(G, S, 1, 1, DEV, group_offset=GOFF, stride=G + 3, extras=("self_slot",))
+    ps.self_slot.copy_(per_group.ints(0, S, u8))
+    fol = e.Follower(ps)
+    fol.term.copy_(per_group.ints(3, 7))
+    fol.state.copy_(pick(per_group, [0, 0, 1, 2, 2, 3], u8))
+    fol.lead.copy_(pick(per_group, [0, S - 1, S - 1, 0xFF, S], u8))
+    resident = [fol.term, fol.state, fol.lead, ps.self_slot]
+    before = [t.clone() for t in resident]
+    g = rnd.ints(0, G)
+    u = torch.rand(n, generator=rnd.gen, device=DEV)
+    inside = u >= 0.04
+    gid = torch.where(inside, GOFF + g, torch.where(u < 0.02, GOFF - 1 - rnd.ints(0, 3),
+                                                    GOFF + G + rnd.ints(0, 3)))
+    p = torch.tensor(TYPE_P, dtype=torch.float32, device=DEV)
+    ty = torch.tensor(TYPES, dtype=u8, device=DEV)[
+        torch.multinomial(p, n, replacement=True, generator=rnd.gen)]
+    frm = torch.where(rnd.hit(0.7), rnd.ints(0, S), pick(rnd, [qm.NONE] * 10 + [S, 200])).to(u8)
+    base = torch.where(inside, fol.term[g], torch.full_like(g, 4))
+    local = (ty == qm.PROP) | (ty == qm.READ_INDEX)
+    other = torch.where(rnd.hit(2 / 7), torch.zeros_like(base), base + pick(rnd, [-1, 0, 0, 0, 1]))
+    term = torch.where(local, torch.where(rnd.hit(0.95), torch.zeros_like(base), base), other)
+    q = dict(group=gid, type=ty, from_=frm, term=term, index=rnd.ints(0, 1 << 62),
+             key=rnd.ints(0, 1 << 62), num_entries=pick(rnd, [0, 1, 1, 2, 7], i32),
+             payload=rnd.ints(0, 1 << 40), cc_count=rnd.ints(0, max_cc + 2, u8))
+    cc = dict(cc_pos=(0, 8, i32), cc_leave=(0, 2, u8), cc_size=(0, 1 << 20, i32))
+    for k, (lo, hi, dt) in cc.items():  # [max_cc][n]
+        q[k] = torch.cat([rnd.ints(lo, hi, dt) for _ in range(max_cc)])
+    runs = []
+    for stats in (None, e.stats_buffer(DEV)):
+        rq = e.Requests(ps, n, max_cc=max_cc)
+        for k, t in q.items():
+            getattr(rq, "q_" + k).copy_(t)
+        rq.n = n
+        props, pm, vm = e.Proposals(ps, max_cc=max_cc), e.PeerMsgs(ps, outputs=False), e.VoteMsgs(ps)
+        out = [props.num_entries, props.payload, props.cc_count, props.cc_pos, props.cc_leave,
+               props.cc_size, rq.ri_request, rq.ri_key, rq.ri_from, vm.type, vm.from_, vm.term,
+               vm.index, vm.log_term, vm.flags, pm.type, rq.p_src, rq.ri_src, rq.v_src, rq.r_src,
+               rq.disposition, rq.deferred_pos, rq.deferred_count]
+        out += [getattr(rq, k) for k in rq.ARRAYS]
+        for t in out:
+            sentinel(t)
+        e.requests(ps, fol, rq, props, pm, vm, stats=stats)
+        runs.append(out)
+    for i, (x, y) in enumerate(zip(*runs)):
+        assert torch.equal(x, y), ("with and without statistics differ", i)
+    for x, y in zip(resident, before):
+        assert torch.equal(x, y), "a resident row was written"
+    # ---- the counters against the outputs ----
+    folded = host(e.stats_reduce(stats))
+    disp = host(rq.disposition)
+    cnt = np.bincount(disp, minlength=256)
+    assert all(cnt[d] > 0 for d in qm.QD_NAMES), {qm.QD_NAMES[d]: int(cnt[d]) for d in qm.QD_NAMES}
+    assert int(cnt.sum()) == n == sum(int(cnt[d]) for d in qm.QD_NAMES)
+    for d, stat in qm.BY_DISPOSITION.items():
+        assert int(folded[stat]) == int(cnt[d]), ("stat", qm.QD_NAMES[d])
+    assert int(folded[qm.STAT_VIOLATIONS]) == int(cnt[qm.BAD]) + int(cnt[qm.REF_PANIC])
+    gh = host(gid)
+    assert int(folded[qm.STAT_GROUPS]) == np.unique(gh[disp == qm.ROUTED]).size
+    with np.errstate(over="ignore"):
+        csum = int(np.add.reduce(qm.record_hashes(gh, disp, host(ty), host(frm))))
+    assert int(folded[qm.STAT_CHECKSUM]) == csum
+    np.testing.assert_array_equal(rq.deferred, np.flatnonzero(disp == qm.DEFERRED))
+    # ---- the output list: one record per FORWARDED / READ_STATE / PROP_DROPPED
+    #      record and per stepped-down MsgReadIndexResp, in list order ----
+    count, got = rq.records()
+    kinds = np.zeros(n, np.uint8)
+    kinds[disp == qm.FORWARDED] = qm.QO_FWD
+    kinds[(disp == qm.READ_STATE) | ((disp == qm.STEPDOWN) & (host(ty) == qm.READ_INDEX_RESP))] = \
+        qm.QO_READ_STATE
+    kinds[disp == qm.PROP_DROPPED] = qm.QO_PROP_DROPPED
+    src = np.flatnonzero(kinds)
+    assert count == src.size > 0 and set(kinds[src]) == {1, 2, 3}
+    np.testing.assert_array_equal(got["src"], src)
+    np.testing.assert_array_equal(got["kind"], kinds[src])

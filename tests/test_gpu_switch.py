@@ -66,13 +66,23 @@ def test_switch_config_matches_oracle(eng, S, F, masks, max_ents, all_groups, ri
     Progress field and ring, the statistics and the algorithmic byte count
     equal the oracle's, over two launches in a row (the second sees the
     first's sends: probes paused, commits already made)."""
-    from tests.test_gpu_progress import ring16_state
+    switch_vs_oracle(eng, S, F, masks, max_ents, all_groups, ring16)
+
+
+def switch_vs_oracle(eng, S, F, masks, max_ents, all_groups, ring16, G=4099, trace=None):
+    """The differential of test_switch_config_matches_oracle on G groups (above
+    4099: the 4099 repeated, widen() of tests/test_gpu_progress.py).  trace: a
+    list that gets, per launch, the device's outputs, state and statistics or
+    byte count, for a caller that compares two launch plans
+    (tests/test_gpu_tiles_per_wave.py)."""
+    from tests.test_gpu_progress import ring16_state, widen
     rng = np.random.default_rng(8100 + 37 * S + F + all_groups + 500 * ring16)
-    G = 4099
-    pb = random_state(rng, G, S, F, 3, masks, EXTRAS, max_ents=max_ents)
+    pb = random_state(rng, min(G, 4099), S, F, 3, masks, EXTRAS, max_ents=max_ents)
     if ring16:  # ABI 8: the 16-bit Inflights form
         ring16_state(rng, pb)
     new_config(rng, pb, masks)
+    if G > pb.G:
+        pb = widen(pb, G)
     ps = to_device(eng, pb, masks, EXTRAS)
     md = orc.mask_dtype(S)
     outcomes = set()
@@ -98,6 +108,9 @@ def test_switch_config_matches_oracle(eng, S, F, masks, max_ents, all_groups, ri
         else:
             got = eng.stats_reduce(st).cpu().numpy().view(np.uint64)
             np.testing.assert_array_equal(got, o.stats, err_msg="stats")
+        if trace is not None:
+            trace.append((sw.result.cpu().numpy(), sw.sent.cpu().numpy(), sw.snap.cpu().numpy(),
+                          ps.host(), got_bytes if acct else got))
         outcomes |= set(int(r) for r in np.unique(o.result))
     want = {1, 3, 4} | ({0} if not all_groups else set())
     assert want <= {r & 0xF for r in outcomes}, outcomes
@@ -137,9 +150,14 @@ def test_become_leader_matches_oracle(eng, S, F, masks, max_ents, reads, ring16)
     (compacted logs: nothing to an inactive peer); every Progress field, the
     log model (runs, term start, lastIndex, committed), the outputs and the
     statistics equal the oracle's."""
+    become_leader_vs_oracle(eng, S, F, masks, max_ents, reads, ring16)
+
+
+def become_leader_vs_oracle(eng, S, F, masks, max_ents, reads, ring16, G=4099, trace=None):
+    """The differential of test_become_leader_matches_oracle on G groups; trace
+    as switch_vs_oracle's."""
     from tests.test_gpu_progress import random_queue, ring16_state
     rng = np.random.default_rng(8300 + 11 * S + F + 500 * ring16)
-    G = 4099
     R = 4
     pb = random_state(rng, G, S, F, R, masks, EXTRAS, max_ents=max_ents)
     if ring16:  # ABI 8: the 16-bit Inflights form (reset empties every ring)
@@ -171,6 +189,9 @@ def test_become_leader_matches_oracle(eng, S, F, masks, max_ents, reads, ring16)
         assert_same(ps, pb)
         got = eng.stats_reduce(st).cpu().numpy().view(np.uint64)
         np.testing.assert_array_equal(got, o.stats, err_msg="stats")
+        if trace is not None:
+            trace.append((ld.result.cpu().numpy(), ld.sent.cpu().numpy(), ld.snap.cpu().numpy(),
+                          ld.pending_conf_index.cpu().numpy(), h, got))
         assert {0, 1, 2, 3} <= set(np.unique(o.result).tolist()) or S == 1
         if bcast:  # (the first election: the second's terms are all new)
             full_same = (el != 0) & (o.result == 1) & (pb.run_count == R) & (term == last_term)

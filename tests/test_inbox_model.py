@@ -184,3 +184,32 @@ def test_checksum_depends_on_position_and_disposition():
     assert len({a, b, c}) == 3
     h = im.mix64((GOFF * im.PHI) ^ im.SALT ^ (im.ROUTED << 56) ^ (im.APP_RESP << 48) ^ (2 << 40))
     assert im.route(st(), [R(2)]).stats[im.STAT_CHECKSUM] == im.mix64(h ^ 0)
+
+
+def test_vectorised_record_hash_equals_the_scalar_one():
+    """record_hashes (what tests/test_gpu_inbox.py sums over a list too long
+    for the model) against record_hash per record on 1500 random records: group
+    ids past 2^33, every disposition and every type byte, slots up to 255; and
+    its sum over a routed list against route()'s STAT_CHECKSUM."""
+    rng = np.random.default_rng(4242)
+    n = 1500
+    group = rng.integers(0, 1 << 62, n, dtype=np.uint64) | np.uint64(1 << 33)
+    disp = rng.choice(list(im.ID_NAMES), n).astype(np.uint8)
+    type_ = rng.integers(0, 256, n).astype(np.uint8)
+    frm = rng.integers(0, 256, n).astype(np.uint8)
+    got = im.record_hashes(group, disp, type_, frm)
+    assert got.dtype == np.uint64 and len(set(got.tolist())) == n
+    assert got.tolist() == [im.record_hash(int(group[i]), int(disp[i]), int(type_[i]),
+                                           int(frm[i]), i) for i in range(n)]
+    G, S = 40, 3
+    s = im.state(num_groups=G, group_offset=GOFF, num_slots=S, stride=G + 3,
+                 term=rng.integers(3, 7, G), state=rng.choice([0, 1, 2, 2, 2, 3], G))
+    recs = [im.rec(GOFF + int(rng.integers(0, G + 1)), int(rng.integers(0, S + 1)),
+                   int(rng.integers(0, 19)), int(rng.integers(2, 8))) for _ in range(n)]
+    o = im.route(s, recs)
+    assert set(o.disposition) == set(im.ID_NAMES)
+    a = lambda k: np.array([m[k] for m in recs], np.uint64)  # noqa: E731
+    with np.errstate(over="ignore"):
+        total = int(np.add.reduce(im.record_hashes(a("group"), np.array(o.disposition, np.uint8),
+                                                   a("type"), a("from"))))
+    assert total == o.stats[im.STAT_CHECKSUM]

@@ -163,3 +163,29 @@ def test_run_to_end_handles_every_record_once():
         done = sum(sum(d != qm.DEFERRED for d in p.disposition) for p in passes)
         assert done == len(recs)
         assert not passes or not passes[-1].deferred
+
+
+def test_vectorised_record_hash_equals_the_scalar_one():
+    """record_hashes (what tests/test_gpu_requests.py sums over a list too
+    long for the model) against record_hash per record on 1500 random records
+    (group ids past 2^33, every disposition, every type and slot byte), and its
+    sum over a handled list against route()'s STAT_CHECKSUM."""
+    import numpy as np
+    rng = np.random.default_rng(4243)
+    n = 1500
+    group = rng.integers(0, 1 << 62, n, dtype=np.uint64) | np.uint64(1 << 33)
+    disp = rng.choice(list(qm.QD_NAMES), n).astype(np.uint8)
+    type_ = rng.integers(0, 256, n).astype(np.uint8)
+    frm = rng.integers(0, 256, n).astype(np.uint8)
+    got = qm.record_hashes(group, disp, type_, frm)
+    assert got.dtype == np.uint64 and len(set(got.tolist())) == n
+    assert got.tolist() == [qm.record_hash(int(group[i]), int(disp[i]), int(type_[i]),
+                                           int(frm[i]), i) for i in range(n)]
+    st, recs = random_case(random.Random(11), G=300, n=n, goff=1 << 33)
+    o = qm.route(st, recs)
+    assert set(o.disposition) == set(qm.QD_NAMES)
+    a = lambda k: np.array([m[k] for m in recs], np.uint64)  # noqa: E731
+    with np.errstate(over="ignore"):
+        total = int(np.add.reduce(qm.record_hashes(a("group"), np.array(o.disposition, np.uint8),
+                                                   a("type"), a("from"))))
+    assert total == o.stats[qm.STAT_CHECKSUM]
