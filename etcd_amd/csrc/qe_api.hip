@@ -82,25 +82,78 @@ using namespace qe;
 
 // The scratch part every list call shares with qe_collect: the chunk offsets
 // (u64, so the scratch is 8-B aligned at the start), then the chunk counts (u32).
-static_assert(kListChunk == kCollectChunk && kIbChunk == kCollectChunk,
-              "k_collect_count's and k_collect_scan's chunks");
+static_assert(kListChunk == kCollectChunk, "k_collect_count's and k_collect_scan's chunks");
 struct ScanScratch {
   int status;  // QE_OK; QE_ERANGE when the chunks pass the 2^31 - 1 blocks of a launch
   uint64_t nb;  // chunks
   uint64_t *offsets;
   uint32_t *counts;
 };
+static uint64_t scan_chunks(uint64_t n) { return (n + kCollectChunk - 1) / kCollectChunk; }
 static ScanScratch scan_scratch(void *scratch, uint64_t n) {
-  const uint64_t nb = (n + kCollectChunk - 1) / kCollectChunk;
+  const uint64_t nb = scan_chunks(n);
   if (nb > 0x7FFFFFFFull) return {QE_ERANGE, 0, nullptr, nullptr};
   uint64_t *offsets = static_cast<uint64_t *>(scratch);
   return {QE_OK, nb, offsets, reinterpret_cast<uint32_t *>(offsets + nb)};
+}
+// k_collect_count: the set flags of each chunk of flags[n].
+static void launch_count(const uint8_t *flags, uint64_t n, const ScanScratch &sc, hipStream_t st) {
+  hipLaunchKernelGGL(k_collect_count, dim3(static_cast<unsigned>((sc.nb + kCountWaves - 1) / kCountWaves)),
+                     dim3(kBlock), 0, st, flags, n, al(flags, 16), sc.nb, sc.counts);
 }
 // k_collect_scan: the exclusive prefix of the chunk counts and the total.
 static int launch_scan(const ScanScratch &sc, uint64_t *total, hipStream_t st) {
   hipLaunchKernelGGL(k_collect_scan, dim3(1), dim3(1024), 0, st, sc.counts, sc.nb, sc.offsets,
                      total);
   return hip_status(hipGetLastError());
+}
+
+// A cursor over a call's scratch: take<T>(k) is the next k elements of T.  Over
+// NULL it only measures, so a call's qe_*_scratch_bytes and the pointers the
+// call uses come from one routine.
+struct Carve {
+  void *base;
+  size_t at = 0;
+  template <class T>
+  T *take(uint64_t k) {
+    T *p = reinterpret_cast<T *>(reinterpret_cast<uintptr_t>(base) + at);
+    at += static_cast<size_t>(k * sizeof(T));
+    return p;
+  }
+};
+
+// qe_inbox's scratch for a.G, a.S and a.n into `a` and `sc` -> its size:
+// qe_collect's part for n flags (offsets u64, counts u32, its 64 B of slack),
+// the words first / stop / hi [G] and cell [S][G], the flags [n].
+static size_t inbox_scratch(void *scratch, IBArgs &a, ScanScratch &sc) {
+  Carve c{scratch};
+  const uint64_t nb = scan_chunks(a.n);
+  sc = {QE_OK, nb, c.take<uint64_t>(nb), c.take<uint32_t>(nb)};
+  c.take<uint8_t>(64);
+  a.first = c.take<uint32_t>(a.G);
+  a.stop = c.take<uint32_t>(a.G);
+  a.hi = c.take<uint32_t>(a.G);
+  a.cell = c.take<uint32_t>(a.S * a.G);
+  a.dflag = c.take<uint8_t>(a.n);
+  return c.at;
+}
+
+// qe_requests's scratch for a.G and a.n into `a`, `sd` (the deferred list) and
+// `so` (the output list) -> its size: the chunk offsets of both lists (u64),
+// their chunk counts (u32), the words stop [G], the flags dflag and okind [n],
+// qe_collect's 64 B of slack per list.
+static size_t requests_scratch(void *scratch, RQArgs &a, ScanScratch &sd, ScanScratch &so) {
+  Carve c{scratch};
+  const uint64_t nb = scan_chunks(a.n);
+  uint64_t *off = c.take<uint64_t>(2 * nb);
+  uint32_t *cnt = c.take<uint32_t>(2 * nb);
+  sd = {QE_OK, nb, off, cnt};
+  so = {QE_OK, nb, off + nb, cnt + nb};
+  a.stop = c.take<uint32_t>(a.G);
+  a.dflag = c.take<uint8_t>(a.n);
+  a.okind = c.take<uint8_t>(a.n);
+  c.take<uint8_t>(2 * 64);
+  return c.at;
 }
 
 // The head the argument struct of every step kernel (qe_follower_step, qe_vote_step,
@@ -962,8 +1015,7 @@ int qe_confchange(const qe_conf *c, const qe_conf_changes *ch, const qe_progress
 }
 
 size_t qe_collect_scratch_bytes(uint64_t num_groups) {
-  const uint64_t nb = (num_groups + kCollectChunk - 1) / kCollectChunk;
-  return static_cast<size_t>(nb * (sizeof(uint32_t) + sizeof(uint64_t)) + 64);
+  return static_cast<size_t>(scan_chunks(num_groups) * (sizeof(uint32_t) + sizeof(uint64_t)) + 64);
 }
 
 int qe_collect(uint64_t num_groups, uint64_t group_offset, const uint64_t *perm,
@@ -977,13 +1029,11 @@ int qe_collect(uint64_t num_groups, uint64_t group_offset, const uint64_t *perm,
   const ScanScratch sc = scan_scratch(scratch, num_groups);
   if (sc.status) return sc.status;
   if (!al(scratch, 8)) return QE_EINVAL;
-  const uint64_t nb = sc.nb;
-  const bool vec = al(flags, 16);
-  hipLaunchKernelGGL(k_collect_count, dim3(static_cast<unsigned>((nb + kCountWaves - 1) / kCountWaves)),
-                     dim3(kBlock), 0, st, flags, num_groups, vec, nb, sc.counts);
+  launch_count(flags, num_groups, sc, st);
   if (const int s = launch_scan(sc, out_count, st)) return s;
-  hipLaunchKernelGGL(k_collect_scatter, dim3(static_cast<unsigned>(nb)), dim3(kBlock), 0, st, flags,
-                     num_groups, vec, group_offset, perm, values, sc.offsets, out_groups, out_values);
+  hipLaunchKernelGGL(k_collect_scatter, dim3(static_cast<unsigned>(sc.nb)), dim3(kBlock), 0, st,
+                     flags, num_groups, al(flags, 16), group_offset, perm, values, sc.offsets,
+                     out_groups, out_values);
   return hip_status(hipGetLastError());
 }
 
@@ -1377,8 +1427,9 @@ int qe_read_states(const qe_progress *p, const qe_read_book *b, const qe_read_st
 
 size_t qe_inbox_scratch_bytes(uint64_t num_groups, uint32_t num_slots, uint64_t num_records) {
   if (num_slots == 0 || num_slots > QE_MAX_SLOTS) return 0;
-  return static_cast<size_t>(4 * (3 + static_cast<uint64_t>(num_slots)) * num_groups +
-                             num_records + qe_collect_scratch_bytes(num_records));
+  IBArgs a{num_groups, 0, 0, num_records, num_slots};  // (G, goff, stride, n, S)
+  ScanScratch sc;
+  return inbox_scratch(nullptr, a, sc);
 }
 
 int qe_inbox(const qe_progress *p, const qe_follower *f, const qe_inbox_in *in,
@@ -1458,36 +1509,25 @@ int qe_inbox(const qe_progress *p, const qe_follower *f, const qe_inbox_in *in,
   a.v_src = out->v_src;
   a.r_src = out->r_src;
   a.disposition = out->disposition;
-  a.deferred = out->deferred;
   a.stats = stats;
-  // scratch: qe_collect's part for n flags (n is in range: its chunks fit a launch), the
-  // words first / stop / hi [G] and cell [S][G], the flags [n]
-  const ScanScratch sc = scan_scratch(scratch, n);
-  const uint64_t nb = sc.nb;
-  a.offsets = sc.offsets;
-  a.first = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(scratch) +
-                                         qe_collect_scratch_bytes(n));
-  a.stop = a.first + a.G;
-  a.hi = a.stop + a.G;
-  a.cell = a.hi + a.G;
-  a.dflag = reinterpret_cast<uint8_t *>(a.cell + a.S * a.G);
+  ScanScratch sc;
+  inbox_scratch(scratch, a, sc);  // (n is in range: its chunks fit a launch)
   int s = dispatch_inbox_init(a, st);
   if (s) return s;
   if (n) {
     s = dispatch_inbox_passes(a, st);
     if (s) return s;
-    const bool vec = (reinterpret_cast<uintptr_t>(a.dflag) % 16) == 0;
-    hipLaunchKernelGGL(k_collect_count, dim3(static_cast<unsigned>((nb + kCountWaves - 1) / kCountWaves)),
-                       dim3(kBlock), 0, st, a.dflag, n, vec, nb, sc.counts);
+    launch_count(a.dflag, n, sc, st);
   }
   s = launch_scan(sc, out->deferred_count, st);
   if (s || !n) return s;
-  return dispatch_inbox_deferred(a, nb, st);
+  return dispatch_route_positions({n, sc.nb, sc.offsets, a.dflag, out->deferred}, st);
 }
 
 size_t qe_requests_scratch_bytes(uint64_t num_groups, uint64_t num_records) {
-  return static_cast<size_t>(4 * num_groups + 2 * num_records +
-                             2 * qe_collect_scratch_bytes(num_records));
+  RQArgs a{num_groups, 0, 0, num_records};  // (G, goff, stride, n)
+  ScanScratch sd, so;
+  return requests_scratch(nullptr, a, sd, so);
 }
 
 int qe_requests(const qe_progress *p, const qe_follower *f, const qe_requests_in *in,
@@ -1565,25 +1605,15 @@ int qe_requests(const qe_progress *p, const qe_follower *f, const qe_requests_in
   a.r_src = out->r_src;
   a.disposition = out->disposition;
   a.stats = stats;
-  // scratch: the chunk offsets of the two lists (u64, n is in range: its chunks fit a
-  // launch), their chunk counts (u32), the words stop [G], the flags dflag and okind [n]
-  const uint64_t nb = (n + kCollectChunk - 1) / kCollectChunk;
-  uint64_t *off = static_cast<uint64_t *>(scratch);
-  uint32_t *cnt = reinterpret_cast<uint32_t *>(off + 2 * nb);
-  const ScanScratch sd{QE_OK, nb, off, cnt}, so{QE_OK, nb, off + nb, cnt + nb};
-  a.stop = cnt + 2 * nb;
-  a.dflag = reinterpret_cast<uint8_t *>(a.stop + a.G);
-  a.okind = a.dflag + n;
+  ScanScratch sd, so;
+  requests_scratch(scratch, a, sd, so);  // (n is in range: its chunks fit a launch)
   int s = dispatch_requests_init(a, st);
   if (s) return s;
   if (n) {
     s = dispatch_requests_passes(a, st);
     if (s) return s;
-    const dim3 grid(static_cast<unsigned>((nb + kCountWaves - 1) / kCountWaves));
-    hipLaunchKernelGGL(k_collect_count, grid, dim3(kBlock), 0, st, a.dflag, n, al(a.dflag, 16), nb,
-                       sd.counts);
-    hipLaunchKernelGGL(k_collect_count, grid, dim3(kBlock), 0, st, a.okind, n, al(a.okind, 16), nb,
-                       so.counts);
+    launch_count(a.dflag, n, sd, st);
+    launch_count(a.okind, n, so, st);
   }
   s = launch_scan(sd, out->deferred_count, st);
   if (s) return s;
@@ -1591,7 +1621,7 @@ int qe_requests(const qe_progress *p, const qe_follower *f, const qe_requests_in
   if (s || !n) return s;
   RQList l{};
   l.G = n;
-  l.nb = nb;
+  l.nb = so.nb;
   l.goff = p->group_offset;
   l.offsets = so.offsets;
   l.flag = a.okind;
@@ -1616,10 +1646,7 @@ int qe_requests(const qe_progress *p, const qe_follower *f, const qe_requests_in
   l.o_src = out->src;
   s = dispatch_requests_out(l, st);
   if (s) return s;
-  l.offsets = sd.offsets;
-  l.flag = a.dflag;
-  l.deferred = out->deferred;
-  return dispatch_requests_deferred(l, st);
+  return dispatch_route_positions({n, sd.nb, sd.offsets, a.dflag, out->deferred}, st);
 }
 
 int qe_stats_reduce(const uint64_t *stats, uint64_t *out, void *stream) {

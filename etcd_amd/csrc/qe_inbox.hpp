@@ -6,9 +6,8 @@
 // opens the wave, a response joins a wave of responses unless its slot is
 // taken, anything else closes the group) has an exact order-free form.  The
 // key of record i is i + 1; key 0 is the virtual MsgHup of a tick.  Four kinds
-// of scratch word per group, all-ones = none, each the result of 32-bit
-// atomicMin (any arrival order gives the same minimum, so the outputs are
-// bit-exact from run to run):
+// of scratch word per group (qe_route.hpp: all-ones = none, each the result of
+// 32-bit atomicMin, so any arrival order gives the same bit-exact outputs):
 //   first[g]    lowest key of any valid record of g;
 //   cell[s][g]  lowest key of a class-R record of g with from = s;
 //   stop[g]     lowest key that ends the wave: a record other than first[g]
@@ -29,26 +28,18 @@
 //   k_inbox_p2     stop and hi (reads f->term);
 //   k_inbox_p3     dispositions, the scatter into the rows, one deferred flag
 //                  byte per record, the statistics;
-//   k_collect_count / k_collect_scan (qe_collect.hpp, unchanged) over the
-//   flags, then k_inbox_deferred: the positions (32-bit) of the flagged records.
-// One lane per record, one wave per 64-record tile: the SoA loads go through
-// per-tile buffer descriptors (coalesced, the ragged last tile clipped).  A
-// record's destination is any group of the batch, so the scatters and the
-// scratch words are addressed with 64-bit pointers under the lane's `valid`
-// predicate (the bounds check: g - group_offset < G, from < S); a 32-bit
-// descriptor offset would not span [S][stride] rows.  In pass 3 nobody reads
-// cell[][]: with statistics, cell[0][g] is the group's "counted" mark
-// (atomicExch: exactly one ROUTED response per group sees it unmarked).
+//   k_collect_count / k_collect_scan (qe_collect.hpp) over the flags, then the
+//   routing layer's k_route_positions: the positions of the flagged records.
+// The lanes, the tiles and the addressing are the routing layer's.  In pass 3
+// nobody reads cell[][]: with statistics, cell[0][g] is the group's "counted"
+// mark (atomicExch: exactly one ROUTED response per group sees it unmarked).
 #pragma once
-#include "qe_step.hpp"
+#include "qe_route.hpp"
 
 namespace qe {
 
 constexpr uint64_t kInboxSalt = 0xD1B54A32D192ED03ull;
-constexpr uint32_t kIbNone = 0xFFFFFFFFu;    // a scratch word nobody lowered
 constexpr uint32_t kIbMarked = 0xFFFFFFFEu;  // cell[0][g] in pass 3: the group is counted
-constexpr uint32_t kIbPer = 16;                // flags per thread and chunk
-constexpr uint32_t kIbChunk = kBlock * kIbPer;  // records per chunk (qe_collect's)
 enum : uint32_t { IB_BAD = 0, IB_F, IB_S, IB_R, IB_V };
 
 struct IBArgs {
@@ -81,23 +72,17 @@ struct IBArgs {
   uint32_t *r_ctx;
   uint32_t *f_src, *s_src, *v_src, *r_src;
   uint8_t *disposition;
-  uint32_t *deferred;
+  uint64_t *stats;
   // scratch
   uint32_t *first, *stop, *hi, *cell;  // [G], [G], [G], [S][G]
   uint8_t *dflag;                      // [n]
-  const uint64_t *offsets;             // k_collect_scan's, per 4096-record chunk
-  uint64_t *stats;
 };
 
-// defined in qe_inst_inbox.hip
+// defined in qe_inst_route.hip
 int dispatch_inbox_init(const IBArgs &a, hipStream_t st);
 int dispatch_inbox_passes(const IBArgs &a, hipStream_t st);
-int dispatch_inbox_deferred(const IBArgs &a, uint64_t nb, hipStream_t st);
 
-// The kernels are not templates (but for the routing pass): they are defined
-// in the one object that launches them, which sets QE_INBOX_KERNELS; qe_api.hip
-// takes the argument struct and the dispatchers above.
-#ifdef QE_INBOX_KERNELS
+#ifdef QE_ROUTE_KERNELS
 
 __device__ __forceinline__ uint32_t inbox_class(uint32_t type) {
   if (type == QE_IMSG_APP || type == QE_IMSG_HEARTBEAT) return IB_F;
@@ -107,24 +92,15 @@ __device__ __forceinline__ uint32_t inbox_class(uint32_t type) {
   return IB_BAD;
 }
 
-// Record `lane` of tile t: its key, group (global and local), slot, type and
-// class, and whether it takes part (rule 2).
-struct IRec {
-  uint32_t key, from, type, cls;
-  uint64_t gid, g;
-  bool live, valid;
+// Record `lane` of tile t: its head, its class and whether it takes part (rule 2).
+struct IRec : RouteRec {
+  uint32_t cls;
+  bool valid;
 };
 __device__ __forceinline__ IRec inbox_rec(const IBArgs &a, uint64_t t, uint32_t lane) {
-  const uint64_t r0 = t * 64;
-  const uint32_t cnt = tile_n(a.n, t);
   IRec r;
-  r.live = lane < cnt;
-  r.key = static_cast<uint32_t>(r0) + lane + 1u;
-  r.gid = bld64<kNT>(mk_rsrc(a.group + r0, cnt * 8), lane * 8);
-  r.from = bld8<kNT>(mk_rsrc(a.from + r0, cnt), lane);
-  r.type = bld8<kNT>(mk_rsrc(a.type + r0, cnt), lane);
+  route_rec(r, a.group, a.from, a.type, a.n, a.goff, t, lane);
   r.cls = inbox_class(r.type);
-  r.g = r.gid - a.goff;
   r.valid = r.live && r.g < a.G && r.cls != IB_BAD && (r.from < a.S || r.type == QE_IMSG_HUP);
   return r;
 }
@@ -135,11 +111,11 @@ __global__ __launch_bounds__(kBlock) void k_inbox_init(IBArgs a) {
   for (uint64_t g = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; g < a.G;
        g += static_cast<uint64_t>(gridDim.x) * kBlock) {
     const bool hup = a.tick && (a.tick[g] & QE_TICK_HUP);
-    a.first[g] = hup ? 0u : kIbNone;
-    a.stop[g] = hup ? 0u : kIbNone;
-    a.hi[g] = kIbNone;
+    a.first[g] = hup ? 0u : kRouteNone;
+    a.stop[g] = hup ? 0u : kRouteNone;
+    a.hi[g] = kRouteNone;
     for (uint32_t s = 0; s < a.S; s++) {
-      a.cell[s * a.G + g] = kIbNone;
+      a.cell[s * a.G + g] = kRouteNone;
       a.r_type[s * a.stride + g] = QE_MSG_NONE;
     }
     a.f_type[g] = QE_LMSG_NONE;
@@ -210,7 +186,7 @@ __global__ __launch_bounds__(kBlock) void k_inbox_p3(IBArgs a) {
     const uint32_t pos = r.key - 1u;
     // ---- the wave, the preamble ----
     const bool isr = r.valid && r.cls == IB_R;
-    uint32_t first = kIbNone, stop = 0, hi = kIbNone, state = 0;
+    uint32_t first = kRouteNone, stop = 0, hi = kRouteNone, state = 0;
     uint64_t rterm = 0;
     if (r.valid) {
       first = a.first[r.g];
@@ -318,9 +294,6 @@ __global__ __launch_bounds__(kBlock) void k_inbox_p3(IBArgs a) {
       // the response that finds cell[0][g] unmarked
       bool counts = routed && !rr;
       if (rr) counts = atomicExch(a.cell + g, kIbMarked) != kIbMarked;
-      const uint64_t h = mix64((r.gid * kPhi) ^ kInboxSalt ^ (static_cast<uint64_t>(disp) << 56) ^
-                               (static_cast<uint64_t>(r.type) << 48) ^
-                               (static_cast<uint64_t>(r.from) << 40));
       const bool bad = r.live && !r.valid;
       cnt[I_GROUPS] += counts ? 1u : 0u;
       cnt[I_ROUTED] += routed ? 1u : 0u;
@@ -330,7 +303,7 @@ __global__ __launch_bounds__(kBlock) void k_inbox_p3(IBArgs a) {
       cnt[I_NOTLEAD] += disp == QE_ID_DROP_NOT_LEADER ? 1u : 0u;
       cnt[I_BAD] += bad ? 1u : 0u;
       cnt[I_VIOL] += bad ? 1u : 0u;
-      cnt[I_CSUM] += r.live ? mix64(h ^ pos) : 0u;
+      cnt[I_CSUM] += r.live ? route_hash(r.gid, kInboxSalt, disp, r.type, r.from, pos) : 0u;
     }
   }
   if (a.stats) {
@@ -343,37 +316,6 @@ __global__ __launch_bounds__(kBlock) void k_inbox_p3(IBArgs a) {
   }
 }
 
-// The positions of the flagged records of chunk blockIdx.x from offsets[chunk]
-// on, ascending: k_collect_scatter's rounds (thread t takes record base + r *
-// kBlock + t, ballot + mbcnt inside the wave, the waves' counts through LDS)
-// with a 32-bit position as the value.
-__global__ __launch_bounds__(kBlock) void k_inbox_deferred(IBArgs a) {
-  __shared__ uint32_t wcnt[kBlock / 64];
-  const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const uint64_t base = static_cast<uint64_t>(blockIdx.x) * kIbChunk;
-  const uint32_t nc =
-      static_cast<uint32_t>(a.n - base < kIbChunk ? a.n - base : kIbChunk);
-  const rsrc_t rfl = mk_rsrc(a.dflag + base, nc);
-  uint64_t pos = a.offsets[blockIdx.x];
-  for (uint32_t r = 0; r < kIbPer; r++) {
-    const uint32_t i = r * kBlock + tid;  // past nc: out of range, reads 0
-    const bool f = bld8<kNT>(rfl, i) != 0;
-    const uint64_t bal = __builtin_amdgcn_ballot_w64(f);
-    const uint32_t rank = __builtin_amdgcn_mbcnt_hi(
-        static_cast<uint32_t>(bal >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(bal), 0u));
-    if (lane == 0) wcnt[w] = static_cast<uint32_t>(__builtin_popcountll(bal));
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < kBlock / 64; k++) {
-      before += k < w ? wcnt[k] : 0u;
-      all += wcnt[k];
-    }
-    if (f) a.deferred[pos + before + rank] = static_cast<uint32_t>(base) + i;
-    pos += all;
-    __syncthreads();  // (the next round overwrites wcnt)
-  }
-}
-#endif  // QE_INBOX_KERNELS
+#endif  // QE_ROUTE_KERNELS
 
 }  // namespace qe

@@ -1,6 +1,7 @@
 // qe_list.hpp — the record-list layer under qe_outbox, qe_replies, qe_ready and
 // qe_read_states: what a call that turns per-group rows into a dense, ordered
-// list of records shares with the others.
+// list of records shares with the others.  The routing layer (qe_route.hpp)
+// uses it with a record of a list as the element in place of a group.
 //
 // Three passes over 4096-group chunks (64 tiles, a block of four waves each):
 //   count   the records of each chunk (list_count_block; qe_ready has a count

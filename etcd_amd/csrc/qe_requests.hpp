@@ -7,9 +7,8 @@
 // The sequential rule (per group, walk the records in list order until the
 // first one that writes a row, which closes the group; every later record of
 // the group is deferred) has an exact order-free form.  The key of record i is
-// i + 1.  One scratch word per group, all-ones = none, the result of 32-bit
-// atomicMin (any arrival order gives the same minimum, so the outputs are
-// bit-exact from run to run):
+// i + 1.  One scratch word per group (qe_route.hpp: all-ones = none, the result
+// of 32-bit atomicMin, so any arrival order gives the same bit-exact outputs):
 //   stop[g]   lowest key of a closer of g: at a leader a valid PROP /
 //             READ_INDEX / TRANSFER_LEADER whose term is 0 or r.Term, in any
 //             state a valid record with term > r.Term.
@@ -23,23 +22,17 @@
 //   k_requests_route  dispositions, the scatter into the rows, two flag bytes
 //                     per record (deferred; the kind of its output record),
 //                     the statistics;
-//   k_collect_count / k_collect_scan (qe_collect.hpp, unchanged) over each of
-//   the two flag arrays, then the fill of the record-list layer (qe_list.hpp)
-//   with a record as the layer's element: k_requests_out writes the output
-//   records, k_requests_deferred the positions of the deferred ones.
-// One lane per record, one wave per 64-record tile: the SoA loads go through
-// per-tile buffer descriptors (coalesced, the ragged last tile clipped).  A
-// record's destination is any group of the batch, so the scatters, the
-// gathers of the receiver's rows and the scratch word are addressed with
-// 64-bit pointers under the lane's predicate (the bounds check: g -
-// group_offset < G, from < S).
+//   k_collect_count / k_collect_scan (qe_collect.hpp) over each of the two flag
+//   arrays, then the fill of the record-list layer (qe_list.hpp) with a record
+//   as the layer's element: k_requests_out writes the output records, the
+//   routing layer's k_route_positions the positions of the deferred ones.
+// The lanes, the tiles and the addressing are the routing layer's.
 #pragma once
-#include "qe_list.hpp"
+#include "qe_route.hpp"
 
 namespace qe {
 
 constexpr uint64_t kRequestsSalt = 0xA24BAED4963EE407ull;
-constexpr uint32_t kRqNone = 0xFFFFFFFFu;  // a stop word nobody lowered
 
 struct RQArgs {
   uint64_t G, goff, stride, n, cc_stride;
@@ -79,13 +72,13 @@ struct RQArgs {
   uint64_t *stats;
 };
 
-// The arguments of the two fills: the layer's element is a record, so its G is
-// the list's length.
+// The arguments of the output list's fill: the layer's element is a record, so
+// its G is the list's length.
 struct RQList {
   uint64_t G, nb, goff;
   const uint64_t *offsets;
   uint64_t *stats;  // NULL: the routing pass holds the statistics
-  const uint8_t *flag;  // [n] okind or dflag
+  const uint8_t *flag;  // [n] okind
   // qe_follower, qe_progress
   const uint64_t *fterm;
   const uint8_t *flead, *self_slot;
@@ -100,46 +93,31 @@ struct RQList {
   uint8_t *o_kind, *o_type, *o_to, *o_from;
   uint64_t *o_term, *o_index, *o_key;
   uint32_t *o_src;
-  uint32_t *deferred;
 };
 
-// defined in qe_inst_requests.hip
+// defined in qe_inst_route.hip
 int dispatch_requests_init(const RQArgs &a, hipStream_t st);
 int dispatch_requests_passes(const RQArgs &a, hipStream_t st);
 int dispatch_requests_out(const RQList &a, hipStream_t st);
-int dispatch_requests_deferred(const RQList &a, hipStream_t st);
 
-// The kernels are no templates: they are defined in the one object that
-// launches them, which sets QE_REQUESTS_KERNELS; qe_api.hip takes the argument
-// structs and the dispatchers above.
-#ifdef QE_REQUESTS_KERNELS
+#ifdef QE_ROUTE_KERNELS
 
-// Record `lane` of tile t: its key, group (global and local), slot, type and
-// term, whether its group is in the batch (ingroup: the receiver's rows may be
-// read) and whether it takes part (valid: rule 1).
-struct QRec {
-  uint32_t key, from, type;
-  uint64_t gid, g, term;
-  bool live, ingroup, valid;
+// Record `lane` of tile t: its head, its term and whether it takes part (rule 1).
+struct QRec : RouteRec {
+  uint64_t term;
+  bool valid;
 };
 __device__ __forceinline__ QRec requests_rec(const RQArgs &a, uint64_t t, uint32_t lane) {
-  const uint64_t r0 = t * 64;
   const uint32_t cnt = tile_n(a.n, t);
   QRec r;
-  r.live = lane < cnt;
-  r.key = static_cast<uint32_t>(r0) + lane + 1u;
-  r.gid = bld64<kNT>(mk_rsrc(a.group + r0, cnt * 8), lane * 8);
-  r.type = bld8<kNT>(mk_rsrc(a.type + r0, cnt), lane);
-  r.from = bld8<kNT>(mk_rsrc(a.from + r0, cnt), lane);
-  r.term = bld64<kNT>(mk_rsrc(a.term + r0, cnt * 8), lane * 8);
-  const uint32_t ne = bld32<kNT>(opt_rsrc(a.num_entries, r0, cnt),
+  route_rec(r, a.group, a.from, a.type, a.n, a.goff, t, lane);
+  r.term = bld64<kNT>(mk_rsrc(a.term + t * 64, cnt * 8), lane * 8);
+  const uint32_t ne = bld32<kNT>(opt_rsrc(a.num_entries, t * 64, cnt),
                                  r.type == QE_QMSG_PROP ? lane * 4 : kOOB);
-  r.g = r.gid - a.goff;
-  r.ingroup = r.live && r.g < a.G;
   const bool known = r.type == QE_QMSG_TRANSFER_LEADER ||
                      (r.type >= QE_QMSG_PROP && r.type <= QE_QMSG_READ_INDEX_RESP);
   const bool local = r.type == QE_QMSG_PROP || r.type == QE_QMSG_READ_INDEX;
-  r.valid = r.ingroup && known && (r.from < a.S || r.from == 0xFFu) &&
+  r.valid = r.live && r.g < a.G && known && (r.from < a.S || r.from == 0xFFu) &&
             !(r.type == QE_QMSG_PROP && ne == 0) && !(local && r.term != 0) &&
             !(r.type == QE_QMSG_TRANSFER_LEADER && r.from == 0xFFu);
   return r;
@@ -156,7 +134,7 @@ __device__ __forceinline__ bool requests_closer(const QRec &r, uint64_t rterm, u
 __global__ __launch_bounds__(kBlock) void k_requests_init(RQArgs a) {
   for (uint64_t g = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; g < a.G;
        g += static_cast<uint64_t>(gridDim.x) * kBlock) {
-    a.stop[g] = kRqNone;
+    a.stop[g] = kRouteNone;
     a.p_num_entries[g] = 0;
     a.ri_request[g] = 0;
     a.v_type[g] = QE_VMSG_NONE;
@@ -192,7 +170,7 @@ __global__ __launch_bounds__(kBlock) void k_requests_route(RQArgs a) {
     const uint32_t n = tile_n(a.n, t);
     const uint32_t pos = r.key - 1u;
     // ---- the receiver's rows, the disposition (rules 2-4) ----
-    uint32_t stop = kRqNone, state = 0, lead = 0xFFu;
+    uint32_t stop = kRouteNone, state = 0, lead = 0xFFu;
     uint64_t rterm = 0;
     if (r.valid) {
       stop = a.stop[r.g];
@@ -287,9 +265,6 @@ __global__ __launch_bounds__(kBlock) void k_requests_route(RQArgs a) {
       if (a.v_src) a.v_src[g] = pos;
     }
     if (a.stats) {
-      const uint64_t h = mix64((r.gid * kPhi) ^ kRequestsSalt ^ (static_cast<uint64_t>(disp) << 56) ^
-                               (static_cast<uint64_t>(r.type) << 48) ^
-                               (static_cast<uint64_t>(r.from) << 40));
       const bool bad = r.live && !r.valid, panic = disp == QE_QD_REF_PANIC;
       cnt[RQ_GROUPS] += routed ? 1u : 0u;  // (a group has one ROUTED record at most)
       cnt[RQ_ROUTED] += routed ? 1u : 0u;
@@ -304,7 +279,7 @@ __global__ __launch_bounds__(kBlock) void k_requests_route(RQArgs a) {
       cnt[RQ_REF_PANIC] += panic ? 1u : 0u;
       cnt[RQ_BAD] += bad ? 1u : 0u;
       cnt[RQ_VIOL] += (bad || panic) ? 1u : 0u;
-      cnt[RQ_CSUM] += r.live ? mix64(h ^ pos) : 0u;
+      cnt[RQ_CSUM] += r.live ? route_hash(r.gid, kRequestsSalt, disp, r.type, r.from, pos) : 0u;
     }
   }
   if (a.stats) {
@@ -316,17 +291,6 @@ __global__ __launch_bounds__(kBlock) void k_requests_route(RQArgs a) {
     wave_stats_add<RQ_N>(cnt, idx, a.stats);
   }
 }
-
-// The counts of the layer: a record's flag byte.
-struct RequestsCounts {
-  const uint8_t *flag;
-  __device__ __forceinline__ void operator()(uint64_t base, uint32_t nc,
-                                             uint32_t (&k)[kListRounds]) const {
-    const rsrc_t rf = mk_rsrc(flag + base, nc);
-#pragma unroll
-    for (uint32_t r = 0; r < kListRounds; r++) k[r] = bld8<kNT>(rf, list_elem(r)) != 0 ? 1u : 0u;
-  }
-};
 
 // Tile t of the list, whose first output record has position tb (rule 5).
 __device__ __forceinline__ void requests_out_tile(const RQList &a, uint64_t t, uint64_t tb,
@@ -369,28 +333,10 @@ __device__ __forceinline__ void requests_out_tile(const RQList &a, uint64_t t, u
   bst32<kNT>(static_cast<uint32_t>(r0) + lane, mk_rsrc(a.o_src + tbc, rem * 4), p4);
 }
 
-// Tile t of the list, whose first deferred record has position tb (its
-// position in `deferred`, which holds n positions: no capacity to enforce).
-__device__ __forceinline__ void requests_deferred_tile(const RQList &a, uint64_t t, uint64_t tb,
-                                                       uint32_t lane, uint64_t (&)[1]) {
-  const uint64_t r0 = t * 64;
-  const uint32_t n = tile_n(a.G, t);
-  const bool has = bld8<kNT>(mk_rsrc(a.flag + r0, n), lane) != 0;
-  const uint32_t pos = lane_rank(__builtin_amdgcn_ballot_w64(has));
-  const auto [tbc, rem] = list_room(tb, a.G, 64);
-  bst32<kNT>(static_cast<uint32_t>(r0) + lane, mk_rsrc(a.deferred + tbc, rem * 4),
-             has ? pos * 4 : kOOB);
-}
-
 __global__ __launch_bounds__(kBlock) void k_requests_out(RQList a) {
   const int idx[1] = {QE_STAT_GROUPS};
-  list_fill_walk<requests_out_tile>(a, idx, RequestsCounts{a.flag});
+  list_fill_walk<requests_out_tile>(a, idx, FlagCounts{a.flag});
 }
-
-__global__ __launch_bounds__(kBlock) void k_requests_deferred(RQList a) {
-  const int idx[1] = {QE_STAT_GROUPS};
-  list_fill_walk<requests_deferred_tile>(a, idx, RequestsCounts{a.flag});
-}
-#endif  // QE_REQUESTS_KERNELS
+#endif  // QE_ROUTE_KERNELS
 
 }  // namespace qe

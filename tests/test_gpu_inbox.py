@@ -276,6 +276,61 @@ def test_inbox_matches_model(eng, G, S, E, n, mode, o):
         np.testing.assert_array_equal(host(t)[: v.size], v.reshape(-1), err_msg="gathered " + k)
 
 
+def three_chunk_list(S, E):
+    """tests/walk.py's three_chunks() as an inbox list over leaders at term 4:
+    a MsgApp opens each hot group (ROUTED, a non-R opener closes its group),
+    responses and votes follow into the hot groups (DEFERRED), and the lone
+    records are of every class, the responses one term below, equal and one
+    above (DROP_LOWER_TERM, ROUTED, STEPDOWN: never DEFERRED)."""
+    from tests import walk
+    G, role, group = walk.three_chunks()
+    lone = [im.APP, im.HEARTBEAT, im.SNAP, im.VOTE, im.APP_RESP, im.HEARTBEAT_RESP, im.HUP]
+    hot = [im.APP_RESP, im.VOTE, im.HEARTBEAT_RESP, im.APP]
+    recs = []
+    for i, (ro, g) in enumerate(zip(role.tolist(), group.tolist())):
+        t = {walk.OPEN: im.APP, walk.HOT: hot[i % 4], walk.LONE: lone[i % 7], walk.OUT: im.APP}[ro]
+        term = 3 + i % 3 if ro == walk.LONE and im.cls_of(t) == im.R_CLS else 4
+        recs.append(im.rec(GOFF + g, i % S, t, term, 1000 + i, 3, 900 + i, i, i, i % 4,
+                           [(1 + i % 7, 4)] * E))
+    return G, group, recs
+
+
+@pytest.mark.parametrize("with_stats", [False, True])
+def test_deferred_positions_over_three_chunks(eng, with_stats):
+    """The deferred list past its second 4096-record chunk (tests/walk.py
+    three_chunks: a chunk whose base comes from two predecessors, a chunk and
+    tiles with no deferred record, a full tile, the ragged last chunk of one
+    record): the dispositions, the count, every deferred position and the
+    poison behind them against the model, with statistics the folded counters
+    and the checksum too."""
+    from tests import walk
+    e, S, E, o = eng, 3, 1, NONE
+    G, group, recs = three_chunk_list(S, E)
+    n, st = len(recs), G + 3
+    rterm, state = np.full(G, 4, np.uint64), np.full(G, im.ST_LEADER, np.uint8)
+    want = im.route(im.state(num_groups=G, group_offset=GOFF, num_slots=S, stride=st, term=rterm,
+                             state=state), recs, None, E)
+    walk.check_three_chunks(want.deferred, group)
+    assert set(want.disposition) == set(im.ID_NAMES) - {im.DROP_NOT_LEADER}
+    ps = e.ProgressState(G, S, 1, 1, DEV, group_offset=GOFF, stride=st)
+    fol = e.Follower(ps)
+    fol.load_host(term=rterm, state=state)
+    ib, rows = fresh_inbox(e, ps, E, o, arrays(recs, E, o["ctx"], o["flags"]), n), Rows(e, ps, fol, E, o)
+    stats = e.stats_buffer(DEV) if with_stats else None
+    e.inbox(ps, fol, ib, rows.lm, rows.sm, rows.vm, rows.pm, stats=stats)
+    disp = host(ib.disposition)
+    np.testing.assert_array_equal(disp[:n], want.disposition, err_msg="disposition")
+    assert kept(disp[n:])
+    count = int(host(ib.deferred_count)[0])
+    assert count == len(want.deferred)
+    dl = host(ib.deferred)
+    np.testing.assert_array_equal(dl[:count], want.deferred, err_msg="deferred")
+    assert kept(dl[count:])
+    if with_stats:
+        folded = host(e.stats_reduce(stats))
+        for i in range(16):
+            assert int(folded[i]) == want.stats.get(i, 0), ("stat", i)
+
 
 def test_route_waves_walk(eng):
     """A list of (2 * cap + 2) tiles and 21 records, cap = the wave count of

@@ -307,6 +307,56 @@ def test_one_follower_forwards_every_record_in_order(eng):
     np.testing.assert_array_equal(got["term"], np.where(np.arange(n) % 3 == 2, 4, 0))
 
 
+def three_chunk_list(S):
+    """tests/walk.py's three_chunks() as a request list: the hot groups lead at
+    term 4, a proposal opens each (ROUTED, which closes its group) and valid
+    requests of every type follow into them (DEFERRED); the groups of the lone
+    records lead and follow in turn and get every type, the read responses at
+    the receiver's term and one above (never DEFERRED: forwarded, routed,
+    answered or a STEPDOWN alone in its group)."""
+    from tests import walk
+    G, role, group = walk.three_chunks()
+    gi = np.arange(G)
+    st = dict(term=np.full(G, 4, np.uint64), lead=np.full(G, 1, np.uint8),
+              state=np.where((gi >= 64) & (gi % 2 == 1), qm.ST_FOLLOWER, qm.ST_LEADER).astype(np.uint8),
+              self_slot=np.full(G, 0, np.uint8))
+    types = [qm.PROP, qm.READ_INDEX, qm.TRANSFER_LEADER, qm.READ_INDEX_RESP]
+    recs = []
+    for i, (ro, g) in enumerate(zip(role.tolist(), group.tolist())):
+        t = qm.PROP if ro in (walk.OPEN, walk.OUT) else types[(i // 2) % 4]
+        frm = i % S if t == qm.TRANSFER_LEADER or i % 3 == 0 else qm.NONE
+        term = 4 + (i // 8) % 2 if t == qm.READ_INDEX_RESP and ro == walk.LONE else 0
+        recs.append(qm.rec(GOFF + g, t, frm, term, 500 + i, 2 * i + 1, 1 + i % 5, i))
+    return G, group, st, recs
+
+
+def test_deferred_positions_over_three_chunks(eng):
+    """The deferred list past its second 4096-record chunk (tests/walk.py
+    three_chunks: a chunk whose base comes from two predecessors, a chunk and
+    tiles with no deferred record, a full tile, the ragged last chunk of one
+    record).  With statistics everything run_and_check compares, the folded
+    counters and the checksum among it; without, the dispositions, the count,
+    every deferred position and the poison behind them."""
+    from tests import walk
+    e, S = eng, 3
+    G, group, st, recs = three_chunk_list(S)
+    n = len(recs)
+    want = qm.route(model_state(G, S, GOFF, st), recs)
+    walk.check_three_chunks(want.deferred, group)
+    assert {qm.ROUTED, qm.STEPDOWN, qm.DEFERRED, qm.FORWARDED, qm.READ_STATE, qm.NO_ARM,
+            qm.BAD} <= set(want.disposition)
+    run_and_check(e, G, S, 0, GOFF, st, recs)
+    ps, fol = setup(e, G, S, GOFF, st)
+    p = Pass(e, ps, fol, recs, 0, n + 5, stats=False)
+    disp = host(p.rq.disposition)
+    np.testing.assert_array_equal(disp[:n], want.disposition, err_msg="disposition")
+    assert kept(disp[n:])
+    assert int(host(p.rq.deferred_count)[0]) == len(want.deferred)
+    dl = host(p.rq.deferred_pos)
+    np.testing.assert_array_equal(dl[:len(want.deferred)], want.deferred, err_msg="deferred")
+    assert kept(dl[len(want.deferred):])
+
+
 def test_deferred_list_fed_back_until_empty_equals_the_model_run_to_the_end(eng):
     e, G, S, max_cc, goff = eng, 64, 5, 2, GOFF
     rng = np.random.default_rng(99)

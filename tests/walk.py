@@ -35,6 +35,48 @@ def walk_groups(cus):
     return (2 * cap + 2) * 64 + 21
 
 
+OPEN, HOT, LONE, OUT = range(4)
+CHUNK = 4096             # records per chunk of a record list's count, scan and fill
+
+
+def three_chunks():
+    """The shape of the deferred-positions lists of tests/test_gpu_inbox.py and
+    tests/test_gpu_requests.py: 3 * CHUNK + 1 records over G = 4200 groups ->
+    (G, role[n], group[n] before the group offset).  A test turns the roles into records of its
+    call: OPEN the first record of a hot group (0..63), which it closes; HOT a
+    later record of a hot group, so DEFERRED; LONE the one record of its group
+    (64..4159), whatever it is; OUT a record outside the batch (group G + 1).
+    Tile 0 opens the hot groups, tile 1 is all HOT, the rest of chunk 0 and
+    chunk 2 are HOT or OUT at random with records 4095, 8192 and 12288 HOT, and
+    chunk 1 is all LONE."""
+    n, G = 3 * CHUNK + 1, 64 + CHUNK + 40
+    rng = np.random.default_rng(4095)
+    role = np.where(rng.random(n) < 0.5, HOT, OUT)
+    role[:64], role[64:128], role[CHUNK:2 * CHUNK] = OPEN, HOT, LONE
+    role[[CHUNK - 1, 2 * CHUNK, 3 * CHUNK]] = HOT
+    i = np.arange(n)
+    group = np.select([role == LONE, role == OUT], [64 + i - CHUNK, G + 1], i % 64)
+    return G, role, group
+
+
+def check_three_chunks(deferred, group):
+    """What the lists of three_chunks() are for, asserted on a model's deferred
+    list: (a) record 4095, the last lane of the last tile of chunk 0, is
+    deferred; (b) no record of chunk 1 is, and each goes to a group no other
+    record touches; (c) record 8192, the first of chunk 2, is; (d) record 12288,
+    the lone record of the ragged last chunk, is; (e) a tile of chunk 0 holds no
+    deferred record and one holds 64."""
+    n = 3 * CHUNK + 1
+    flag = np.zeros(n, bool)
+    flag[np.asarray(deferred, np.int64)] = True
+    assert len(group) == n and flag[CHUNK - 1] and flag[2 * CHUNK] and flag[3 * CHUNK]
+    assert not flag[CHUNK:2 * CHUNK].any()
+    assert (np.bincount(group)[group[CHUNK:2 * CHUNK]] == 1).all()
+    per_tile = flag[:CHUNK].reshape(-1, 64).sum(axis=1)
+    assert (per_tile == 0).any() and (per_tile == 64).any()
+    assert flag[2 * CHUNK + 1:3 * CHUNK].any() and not flag[2 * CHUNK + 1:3 * CHUNK].all()
+
+
 def repeat(arrays, G, stride, rows=(), fill=0):
     """The base's packed arrays (dict, base stride PERIOD) with period PERIOD
     up to G groups.  rows: {name: row count} of the [rows][stride] arrays, or
