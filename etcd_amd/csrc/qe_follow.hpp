@@ -116,7 +116,8 @@ __global__ __launch_bounds__(kBlock) void k_follow(FArgs a) {
         nent += len[j];
       }
       const uint64_t lastnew = index + nent;
-      bad = bad || lastnew < index;
+      // 2^64 - 1 is no log index (the ci = kInf below, li + 1, Next on the leader's side)
+      bad = bad || lastnew < index || lastnew == kInf;
       const bool lower = mterm < term, higher = mterm > term;
       const bool lead_same = !lower && !higher && st == QE_STATE_LEADER;
       const bool proceed = has && !bad && !lower && !lead_same;

@@ -175,8 +175,15 @@ __device__ __forceinline__ void ready_tile(const RDArgs &a, uint64_t t, uint64_t
   uint64_t ent_count, ent_last, apply_count;
   RunCut<(E > 0 ? E : 1)> ec, ac;
   if constexpr (E > 0) {
-    ec = run_cut<RM, E>(rf, rt, nr, li, stable, li, ents);
-    ac = run_cut<RM, E>(rf, rt, nr, li, off - 1, ahi, apply);
+    // a list holds 0xFFFFFFFF entries at most (qe_outbox rule 4): every ent_len
+    // is a uint32, and run_cut takes a run's length from the low dwords.  The
+    // cap in outbox_tile's wrap-safe form.  The apply list is cut first: with
+    // the entries first k_ready_fill<4, 4> takes 129 VGPRs, a wave per SIMD less
+    constexpr uint64_t lim = 0xFFFFFFFFull;
+    const uint64_t chi = ahi - (off - 1) > lim ? off - 1 + lim : ahi;
+    ac = run_cut<RM, E>(rf, rt, nr, li, off - 1, chi, apply);
+    const uint64_t ehi = li - stable > lim ? stable + lim : li;
+    ec = run_cut<RM, E>(rf, rt, nr, li, stable, ehi, ents);
     ent_count = ec.ents;
     ent_last = ec.last;
     apply_count = ac.ents;

@@ -240,7 +240,8 @@ __global__ __launch_bounds__(kBlock) void k_snap(SNArgs a) {
       const uint32_t st = bld8<kNT>(mk_rsrc(a.state + g0, n), h1);
       const uint64_t sindex = bld64<kNT>(mk_rsrc(a.sindex + g0, n * 8), h8);
       const uint64_t committed = bld64<kNT>(mk_rsrc(a.committed + g0, n * 8), h8);
-      const bool bad = has && (ty != QE_SMSG_SNAP || from >= a.S);
+      // 2^64 - 1 is no log index: first_index = sindex + 1 would wrap
+      const bool bad = has && (ty != QE_SMSG_SNAP || from >= a.S || sindex == kInf);
       const bool lower = mterm < term, higher = mterm > term;
       const bool lead_same = !lower && !higher && st == QE_STATE_LEADER;
       const bool proceed = has && !bad && !lower && !lead_same;

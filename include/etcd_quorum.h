@@ -754,8 +754,12 @@ int qe_tick(const qe_progress *p, const qe_timers *t, const qe_tick_out *out,
  * run_first[0] the dummy (snapshot) index, term(i) = run_term of the highest
  * run r < run_count with run_first[r] <= i, and 0 outside [run_first[0],
  * last_index] (raft/log.go:265-285).  The caller keeps raftLog's invariant
- * run_first[0] <= committed <= last_index, run_first ascending, run_count in
- * 1..log_runs (results are unspecified otherwise; memory stays in bounds).
+ * run_first[0] <= committed <= last_index < 2^64 - 1, run_first ascending,
+ * run_count in 1..log_runs (results are unspecified otherwise; memory stays in
+ * bounds).  2^64 - 1 is QE_INDEX_INF here as everywhere else in this ABI: the
+ * reference cannot continue past it (Next = lastIndex + 1 and firstIndex =
+ * snapshot index + 1 wrap), so no message may bring a log there (rule 2, and
+ * qe_snapshot_step's).
  * Rows r >= run_count[g] are not state: the call may leave or overwrite them.
  *
  * Per group, in this order (m = the message, r = the group):
@@ -763,7 +767,8 @@ int qe_tick(const qe_progress *p, const qe_timers *t, const qe_tick_out *out,
  *     read or written (but events[g] = 0, see below).
  *  2. QE_FR_BAD_MSG (refused): an unknown type, from >= num_slots, and for a
  *     MsgApp a run with ent_len > 0 and ent_term 0, run terms that decrease
- *     (over the runs with ent_len > 0), or index + n wrapping.
+ *     (over the runs with ent_len > 0), or index + n wrapping or reaching
+ *     2^64 - 1 (QE_INDEX_INF is no log index: see the invariant above).
  *  3. m.term < r.term (:883-919): with QE_FOLLOW_CHECK_QUORUM or
  *     QE_FOLLOW_PREVOTE QE_FR_LOWER_TERM_RESP (the empty MsgAppResp of :906),
  *     else QE_FR_IGNORED.  Nothing changes, no event.
@@ -1548,7 +1553,9 @@ int qe_compact(const qe_progress *p, const qe_compaction *c, uint64_t *stats, vo
  * Per group, in this order (m = the message, r = the group):
  *  1. type == QE_SMSG_NONE: QE_SR_NONE, nothing else of the group is read or
  *     written (but events[g] = 0).
- *  2. QE_SR_BAD_MSG (refused): an unknown type or from >= num_slots.
+ *  2. QE_SR_BAD_MSG (refused): an unknown type, from >= num_slots, or
+ *     snap_index == 2^64 - 1 (QE_INDEX_INF is no log index: first_index =
+ *     snap_index + 1 would wrap).
  *  3. The preamble, as steps 3-5 of qe_follower_step, except that m.term <
  *     r.term is ALWAYS QE_SR_IGNORED, whatever CheckQuorum and PreVote say:
  *     :884 lists only MsgApp and MsgHeartbeat (so qe_follower's flags are not
@@ -2129,7 +2136,10 @@ int qe_replies(const qe_progress *p, const qe_replies_in *in, const qe_replies_o
  *     soft = (lead, state); soft_changed = soft != (prev_lead, prev_state).
  *  2. Entries = (stable, last_index]: ent_first = stable + 1 (in every
  *     record).  With ent_runs E > 0 they are cut into the table's term runs
- *     exactly as qe_outbox rule 4 cuts a MsgApp with index = stable: run j is
+ *     exactly as qe_outbox rule 4 cuts a MsgApp with index = stable and
+ *     max_entries 0, its cap of 0xFFFFFFFF entries included: the range listed
+ *     is (stable, min(last_index, stable + 0xFFFFFFFF)], so every ent_len fits
+ *     its uint32.  Run j is
  *     the j-th table run that overlaps the range, ent_len[j*capacity+i] its
  *     overlap, ent_term[j*capacity+i] its term; the list ends after E runs and
  *     QE_RD_ENTS_CUT is set when it ends below last_index.  ent_count = the
@@ -2142,7 +2152,8 @@ int qe_replies(const qe_progress *p, const qe_replies_in *in, const qe_replies_o
  *     + 1); if committed + 1 > off they are [off, hi], hi = committed, or off +
  *     max_apply - 1 when max_apply is nonzero and smaller (the entry-count
  *     model of maxNextEntsSize, as max_ents models MaxSizePerMsg).  With E > 0
- *     they are cut into term runs as the entries are (apply_len / apply_term,
+ *     they are cut into term runs as the entries are, 0xFFFFFFFF entries from
+ *     off at most (apply_len / apply_term,
  *     a second [E][capacity] pair) and end after E runs.  apply_count = the
  *     entries listed, apply_first = off (0 with apply_count 0);
  *     QE_RD_APPLY_CUT is set when the list ends below committed.

@@ -223,7 +223,7 @@ def bad_msg(m, num_slots):
                     return True
                 prev = t
             n += ln
-        if m.index + n > M64:
+        if m.index + n >= M64:  # wrapping, or reaching 2^64 - 1: no log index
             return True
     return False
 

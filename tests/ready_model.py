@@ -62,8 +62,9 @@ def note(st, rs, follow_result=None, append_from=None, snap_result=None, snap_re
 
 def cut(runs, li, i, hi, ent_runs):
     """(i, hi] cut into the table's runs, at most ent_runs of them (qe_outbox
-    rule 4) -> [(len, term), ...]."""
+    rule 4, its cap of 0xFFFFFFFF entries included) -> [(len, term), ...]."""
     out = []
+    hi = min(hi, i + 0xFFFFFFFF)
     for r, (f, t) in enumerate(runs):
         end = runs[r + 1][0] - 1 if r + 1 < len(runs) else li
         lo, e = max(f, i + 1), min(end, hi)

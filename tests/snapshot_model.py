@@ -194,7 +194,7 @@ def step(sn, m, num_slots=16, log_runs=16):
     out = {"result": SR_NONE, "events": 0}
     if m.type == SMSG_NONE:
         return sn, out
-    if m.type != SMSG_SNAP or m.frm >= num_slots:
+    if m.type != SMSG_SNAP or m.frm >= num_slots or m.sindex >= M64:  # 2^64 - 1: no log index
         out["result"] = SR_BAD_MSG
         return sn, out
     node = sn.node

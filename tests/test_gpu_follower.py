@@ -11,6 +11,7 @@ import torch
 from oracle import orc
 from tests import follower_model as fm
 from tests import follower_traces as ft
+from tests import lift
 from tests.golden_util import raft_tables
 from tests.test_follower_model import fixture_cases, tables
 from tests.test_gpu_progress import DEV, eng  # noqa: F401
@@ -202,6 +203,51 @@ def test_random_differential(eng, R, E, flags, vote):
     want |= {fm.FR_LOWER_TERM_RESP} if flags else set()
     want |= {fm.FR_RUNS_FULL, fm.FR_APP_GAP} if E else set()
     assert want <= seen, sorted(fm.FR_NAMES[c] for c in want - seen)
+
+
+@pytest.mark.parametrize("case", lift.FOLLOWER_CASES, ids=str)
+def test_wide_differential(eng, case):
+    """The random differential with every group's indexes and terms lifted
+    (tests/lift.py): a base per group out of 0, 2^32 - k, 2^53 + 1, 2^63 - k and
+    2^64 - 4096 for each, so the high dword of every state, message and output
+    word is live, logs cross the dword boundary and the int64 sign bit.  Nine
+    tiles and a ragged one, 8 consecutive calls, statistics on; the model runs
+    on the wide values themselves.  tests/test_lift_model.py proves the run's
+    coverage on the CPU; it is asserted again on what the device went through."""
+    R, E, flags = case
+    box = {}
+
+    def stepper(nodes, msgs):
+        if not box:
+            box["h"] = Harness(eng, nodes, R, lift.FOLLOWER_S, stride=lift.G + lift.PAD,
+                               flags=flags, goff=lift.GOFF)
+        outs = box["h"].step(msgs, E)
+        return box["h"].nodes, outs
+
+    ls, log = lift.follower_run(case, stepper)
+    lift.check_follower_coverage(case, ls, log)
+
+
+def test_top_of_range(eng):
+    """2^64 - 1 is QE_INDEX_INF and no log index: the rows of
+    lift.follower_top_rows() at lane 0, 63, 64 and the last lane of a partial
+    tile among random lifted neighbours.  The harness holds the device to the
+    model; the rows' literals hold the model."""
+    rng = np.random.default_rng(83)
+    G, R, S, E = 64 * 2 + 37, 8, 3, 4
+    spots = (0, 63, 64, G - 1)
+    results = []
+    for row in lift.follower_top_rows():
+        nodes, msgs = lift.follower_neighbours(rng, G, R, S, E)
+        for pos in spots:
+            nodes[pos], msgs[pos] = row[1], row[2]
+        h = Harness(eng, nodes, R, S, stride=G + 5, flags=int(rng.integers(0, 4)), goff=1 << 33)
+        outs = h.step(msgs, E)
+        for pos in spots:
+            lift.check_follower_top_row(row, row[1], h.nodes[pos], outs[pos])
+        assert len({repr(sorted(outs[p].items())) for p in spots}) == 1, row[0]
+        results.append(outs[0]["result"])
+    assert results == lift.FOLLOWER_TOP_RESULTS
 
 
 def test_one_group_and_all_none(eng):

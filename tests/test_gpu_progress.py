@@ -29,12 +29,13 @@ def eng():
     return engine
 
 
-def random_state(rng, G, S, F, R, masks, extras=(), max_ents=0, base=0):
+def random_state(rng, G, S, F, R, masks, extras=(), max_ents=0, base=0, tbase=0):
     """A random leader-side state.  `base` shifts every log index (ABI 4:
     near a 2^32 boundary the Inflights rings straddle two epochs, past 2^43
-    every ring is wide)."""
+    every ring is wide); `tbase` shifts every run's term, the dummy entry's
+    among them (and random_msgs every LogTerm that is not 0)."""
     pb = orc.ProgressBatch(G, S, F, R, max_ents=max_ents)
-    pb.base = base
+    pb.base, pb.tbase = base, tbase
     # leader log: runs over [dummy, last]
     for g in range(G):
         nr = int(rng.integers(1, R + 1))
@@ -94,6 +95,8 @@ def random_state(rng, G, S, F, R, masks, extras=(), max_ents=0, base=0):
         pb.pending = np.where(pb.pending != 0, pb.pending + b, pb.pending).astype(np.uint64)
         if pb.snap_index is not None:
             pb.snap_index = (pb.snap_index + b).astype(np.uint64)
+    if tbase:
+        pb.run_term = (pb.run_term + np.uint64(tbase)).astype(np.uint64)
     return pb
 
 
@@ -106,6 +109,9 @@ def random_msgs(rng, pb):
                       lo + (rng.random(n) * (li - lo + 3)).astype(np.uint64)).astype(np.uint64)
     mhint = (lo + (rng.random(n) * (li - lo + 2)).astype(np.uint64)).astype(np.uint64)
     mlogterm = np.where(rng.random(n) < 0.3, 0, rng.integers(1, 10, n)).astype(np.uint64)
+    tb = np.uint64(getattr(pb, "tbase", 0))
+    if tb:  # (0 stays 0: a reject without a LogTerm)
+        mlogterm = np.where(mlogterm != 0, mlogterm + tb, mlogterm).astype(np.uint64)
     return mtype, mindex, mhint, mlogterm
 
 
@@ -451,6 +457,66 @@ def test_progress_rings_across_epochs(eng, base, F):
         assert_same(ps, pb)
         wide_seen += int(((ps.peer & 16) != 0).sum())
     assert wide_seen > 0
+
+
+def term_crossings(pb, mtype, mhint, mlogterm, bound):
+    """How many rejects of a round start the leader's findConflictByTerm walk
+    (raft/log.go:147-168) on an entry whose term is >= bound while the
+    message's LogTerm is below it, so that the walk's `term(index) > LogTerm`
+    compares across `bound`: counted from the oracle's state before the step
+    (term() restated over the run rows; tests/test_progress_oracle.py pins the
+    oracle's own to the reference)."""
+    G, S, R = pb.G, pb.S, pb.R
+    rf, rt = pb.run_first.reshape(R, G), pb.run_term.reshape(R, G)
+    live = np.arange(R)[:, None] < pb.run_count[None, :].astype(np.int64)
+    n = 0
+    for s in range(S):
+        rows = slice(s * G, (s + 1) * G)
+        hint, lt = mhint[rows], mlogterm[rows]
+        at = live & (rf <= hint[None, :])
+        last_run = np.where(at.any(axis=0), R - 1 - np.argmax(at[::-1], axis=0), 0)
+        term = np.where(at.any(axis=0) & (hint <= pb.last_index), rt[last_run, np.arange(G)], 0)
+        tracked = np.ones(G, bool) if pb.tracked is None else (pb.tracked.astype(np.int64) >> s) & 1 != 0
+        n += int(((mtype[rows] == 2) & (lt != 0) & (lt < bound) & (term >= bound) & tracked).sum())
+    return n
+
+
+@pytest.mark.parametrize("R", [3, 6, 9])
+@pytest.mark.parametrize("tbase", [(1 << 32) - 3, (1 << 63) - 3])
+def test_progress_terms_past_32_bits(eng, tbase, R):
+    """Every run term and LogTerm shifted by `tbase`: run terms straddle 2^32
+    (2^63: the sign bit of the int64 tensors) inside one table, so the leader's
+    findConflictByTerm and the log-term compare of a reject see terms on both
+    sides of it.  Step, send and the instrumented byte count on odd rounds
+    against the oracle, and at least one reject whose walk starts on a term at
+    or past the boundary with a LogTerm below it."""
+    rng = np.random.default_rng(tbase % 1000 + R)
+    G, S, F = 3001, 5, 8
+    pb = random_state(rng, G, S, F, R, (), EXTRAS, max_ents=int(rng.integers(0, 4)), tbase=tbase)
+    ps = to_device(eng, pb, (), EXTRAS)
+    md = orc.mask_dtype(S)
+    bound, crossings = (tbase + 3), 0
+    for rnd in range(3):
+        mtype, mindex, mhint, mlogterm = random_msgs(rng, pb)
+        crossings += term_crossings(pb, mtype, mhint, mlogterm, bound)
+        msgs = load_msgs(eng, ps, mtype, mindex, mhint, mlogterm)
+        if rnd % 2:
+            msgs.bytes_requested = torch.zeros(1, dtype=torch.int64, device=DEV)
+        eng.progress_step(ps, msgs)
+        o = orc.progress_step(pb, mtype, mindex, mhint, mlogterm, count_bytes=True)
+        assert_same(ps, pb)
+        assert_outputs(msgs, o, S)
+        if rnd % 2:
+            assert int(msgs.bytes_requested.item()) == int(o.bytes[0])
+        want = rng.integers(0, 1 << S, G).astype(md)
+        sei, me = int(rnd % 2), int(rng.integers(0, 5))
+        ps.max_ents = pb.max_ents = me
+        sent, snap = eng.progress_send(ps, to_dev_mask(want, S), sei)
+        o_sent, o_snap = orc.progress_send(pb, want, sei)
+        np.testing.assert_array_equal(sent.cpu().numpy().view(md), o_sent)
+        np.testing.assert_array_equal(snap.cpu().numpy().view(md), o_snap)
+        assert_same(ps, pb)
+    assert crossings > 0
 
 
 @pytest.mark.parametrize("R", [8, 9, 16])

@@ -14,12 +14,16 @@ tests/ready_model.py.
    engine beside the models, TraceDeviceBackend's comparisons still running):
    base 0 and 61, the 16-bit ring form where RUNS <= 4.
 4. A closed loop on tests/cluster_sim: ready + advance every round, a Storage
-   per node rebuilt from the records alone (tests/ready_sim.ReadySim)."""
+   per node rebuilt from the records alone (tests/ready_sim.ReadySim).
+5. Wide values: the differential of 1 on logs at 2^32 - k, 2^53, 2^63 - k and
+   2^64 - 4096 with terms as wide (test_wide_differential), and ranges of 2^32
+   entries and more, which a list caps at 0xFFFFFFFF (test_top_of_range)."""
 import numpy as np
 import pytest
 import torch
 
 from tests import cluster_sim as cs
+from tests import lift
 from tests import ready_model as rdm
 from tests import ready_sim as rsim
 from tests import trace_cluster as tc
@@ -53,24 +57,33 @@ def none_or_slot(rng, n):
     return np.where(rng.random(n) < 0.4, rng.integers(S, 256, n), v).astype(np.uint8)
 
 
-def random_state(rng, G, R):
+def random_state(rng, G, R, bases=None, tbases=(0,)):
     """-> (st, rs): valid logs (run_first ascending, run_first[0] <= committed
-    <= last_index, run_first[0] <= stable), about half of the groups quiet."""
+    <= last_index, run_first[0] <= stable), about half of the groups quiet.
+    The dummy index is below 50, or for three groups in ten 2^32 - 3; with
+    `bases` it is one of them per group plus a draw below 50, and every
+    run_term, term and prev_term lies above one of `tbases` (cycling so that
+    every base meets every term base).  Every draw is relative to the group's
+    base, so without `bases` the stream is the one it has always been."""
     st_ = G + 3
     u64 = np.uint64
     rf = np.full(R * st_, 0x0E0E0E0E0E0E0E0E, u64)
     rt = np.full(R * st_, 0x0E0E0E0E0E0E0E0E, u64)
     nr = rng.integers(1, R + 1, G).astype(np.uint8)
     last, com = np.zeros(G, u64), np.zeros(G, u64)
-    base = np.where(rng.random(G) < 0.3, (1 << 32) - 3, rng.integers(0, 50, G)).astype(u64)
+    if bases is None:
+        base = np.where(rng.random(G) < 0.3, (1 << 32) - 3, rng.integers(0, 50, G)).astype(u64)
+    else:
+        base = np.array([bases[g % len(bases)] + int(rng.integers(0, 50)) for g in range(G)], u64)
+    nb = len(bases) if bases is not None else 1
     for g in range(G):
-        f, t = int(base[g]), int(rng.integers(0, 4))
+        f, t = int(base[g]), int(rng.integers(0, 4)) + tbases[(g // nb) % len(tbases)]
         for r in range(int(nr[g])):
             rf[r * st_ + g], rt[r * st_ + g] = f, t
             f += int(rng.integers(1, 5))
             t += int(rng.integers(1, 3))
         last[g] = f - 1 + int(rng.integers(0, 8))
-        com[g] = rng.integers(int(base[g]), int(last[g]) + 1)
+        com[g] = int(base[g]) + int(rng.integers(0, int(last[g]) + 1 - int(base[g])))
     top = np.array([rt[(int(nr[g]) - 1) * st_ + g] for g in range(G)], u64)
     st = rdm.state(num_groups=G, group_offset=GOFF, num_slots=S, stride=st_, log_runs=R,
                    committed=com, last_index=last, run_first=rf, run_term=rt, run_count=nr,
@@ -88,16 +101,17 @@ def random_state(rng, G, R):
     for g in np.flatnonzero(loud):
         b, li, c = int(base[g]), int(last[g]), int(com[g])
         k = rng.integers(0, 8)
+        lo = 0 if bases is None else b - min(b, 5)       # (a few indexes below the dummy)
         if k == 0:
-            rs.stable[g] = rng.integers(b, li + 1)
+            rs.stable[g] = b + int(rng.integers(0, li + 1 - b))
         elif k == 1:
-            rs.applied[g] = rng.integers(0, c + 2)      # below the dummy, inside, past committed
+            rs.applied[g] = lo + int(rng.integers(0, c + 2 - lo))  # below the dummy, inside, past committed
         elif k == 2:
             rs.snap_pending[g] = rng.integers(1, 1 << 40)
         elif k == 3:
             rs.prev_term[g] = max(0, int(st.term[g]) - 1)
         elif k == 4:
-            rs.prev_commit[g] = rng.integers(0, c + 1)
+            rs.prev_commit[g] = lo + int(rng.integers(0, c + 1 - lo))
         elif k == 5:
             rs.prev_vote[g] = rng.integers(0, 256)
         elif k == 6:
@@ -248,6 +262,138 @@ def test_random_differential(eng, G, R, E):  # noqa: F811
     rd = filled_ready(eng, ps, G, E)
     eng.ready(ps, d.fol, d.rs, rd)
     assert records_of(rd) == (len(want), want)
+
+
+@pytest.mark.parametrize("E", (0, 4))
+def test_wide_differential(eng, E):  # noqa: F811
+    """qe_ready and qe_advance as in test_random_differential, on logs whose
+    dummy index lies at 0, 2^32 - k, 2^53 + 1, 2^63 - k or 2^64 - 4096 and
+    whose terms lie above 0, 2^32 - k, 2^63 - k or 2^64 - 4096 (tests/lift.py's
+    bases, every index base with every term base): run_cut, rd_flags' applied + 1
+    / run_first[0] + 1 / committed + 1 and qe_advance's range checks on words
+    whose high dword is live, that cross 2^32 inside a log and pass the int64
+    sign bit."""
+    G, R = 130, 4
+    rng = np.random.default_rng(77000 + E)
+    st, rs = random_state(rng, G, R, bases=lift.IB, tbases=lift.TB)
+    assert (st.last_index >> np.uint64(63)).any() and (st.term >> np.uint64(63)).any()
+    assert ((st.run_first.reshape(R, -1)[0, :G] >> np.uint64(32)) !=
+            (st.last_index >> np.uint64(32))).any()  # a log across a dword boundary
+    d = Dev(eng, st, rs)
+    ps = d.ps
+    pend = (rng.random(G) < 0.05).astype(np.uint8) * rng.integers(1, 256, G).astype(np.uint8)
+    full = None
+    for pending, max_apply in ((None, 0), (pend, 0), (None, 3), (pend, 3)):
+        want, wstats = rdm.ready(st, rs, pending=pending, max_apply=max_apply, ent_runs=E)
+        n = len(want)
+        assert 0 < n < G
+        for cap in (n // 2, n):
+            rd = filled_ready(eng, ps, cap, E)
+            stats = eng.stats_buffer(DEV)
+            before = d.snapshot()
+            eng.ready(ps, d.fol, d.rs, rd, pending=None if pending is None else up(pending),
+                      max_apply=max_apply, stats=stats)
+            count, got = records_of(rd)
+            assert count == n
+            assert got == want[:cap]
+            past_is_fill(rd, min(n, cap))
+            d.unchanged(before)
+            folded = host(eng.stats_reduce(stats))
+            for k, v in wstats.items():
+                assert int(folded[k]) == v & rdm.M64, (k, cap)
+            if pending is None and max_apply == 0 and cap == n:
+                full = rd
+    want, _ = rdm.ready(st, rs, max_apply=3, ent_runs=E)
+    assert any(r["flags"] & rdm.APPLY_CUT for r in want)
+    assert any(r["ent_count"] and r["ent_first"] >> 32 for r in want)
+    assert any(r["apply_count"] and r["apply_first"] >> 63 for r in want)
+    # ---- qe_advance on the list qe_ready left on the device ----
+    want, _ = rdm.ready(st, rs, ent_runs=E)
+    al = (rng.random(G) < 0.8).astype(np.uint8)
+    pci = np.array([int(c) - min(int(c), 2) + int(rng.integers(0, 4)) for c in st.committed],
+                   np.uint64)
+    pci = np.where(rng.random(G) < 0.7, rs.applied, pci)
+    before = d.snapshot()
+    res = eng.advance(ps, d.rs, full, fol=d.fol, auto_leave=up(al), pending_conf_index=up(pci))
+    wres = rdm.advance(st, rs, want, auto_leave=al, pending_conf_index=pci)
+    np.testing.assert_array_equal(host(res)[:len(want)], wres)
+    assert (host(res)[len(want):] == FILL).all()
+    assert rdm.ADV_APPLIED_RANGE in wres and rdm.ADV_OK in wres
+    assert any(x & rdm.ADV_AUTO_LEAVE for x in wres)
+    d.same_rows(rs)
+    d.unchanged(before, but={"rs_" + k for k in rdm.STATE_ROWS})
+    want, _ = rdm.ready(st, rs, ent_runs=E)
+    rd = filled_ready(eng, ps, G, E)
+    eng.ready(ps, d.fol, d.rs, rd)
+    assert records_of(rd) == (len(want), want)
+
+
+TOP = 0xFFFFFFFF
+
+
+def top_rows():
+    """The hand-built rows of test_top_of_range -> [(id, D, kind, runs)]: a
+    range of D entries to persist (kind "ents": stable = the dummy index) or to
+    apply ("apply": applied = the dummy index, max_apply 0), over a table of one
+    run or of two with the second starting inside the range."""
+    rows = []
+    for D in (TOP, TOP + 1, TOP + 6, 1 << 33):
+        for kind in ("ents", "apply"):
+            for two in (True, False):
+                rows.append((f"{kind} {D:#x} {'two runs' if two else 'one run'}", D, kind, two))
+    return rows
+
+
+def put_top_row(st, rs, g, row, f0=(1 << 40) + 7):
+    _, D, kind, two = row
+    s = st.stride
+    st.run_first[g], st.run_term[g] = f0, (1 << 32) + 3
+    st.run_first[s + g], st.run_term[s + g] = f0 + D // 2 + 3, (1 << 32) + 4
+    st.run_count[g] = 2 if two else 1
+    st.last_index[g] = f0 + D
+    st.term[g] = (1 << 32) + 4
+    st.committed[g] = rs.stable[g] = f0 + D if kind == "apply" else f0
+    rs.applied[g] = f0
+    rs.prev_term[g], rs.prev_commit[g] = st.term[g], st.committed[g]
+    rs.snap_pending[g] = 0
+
+
+def test_top_of_range(eng):  # noqa: F811
+    """A list holds 0xFFFFFFFF entries at most (qe_outbox rule 4): ranges of
+    2^32 - 1, 2^32, 2^32 + 5 and 2^33 entries to persist and to apply, over one
+    table run and over two, each at lane 0, 63, 64 and the last lane of a
+    partial tile among random neighbours, with E = 4 and with E = 0, where the
+    range stays whole.  The model takes the same cap (tests/test_lift_model.py
+    pins it); the literals below hold for the range of 2^32 over one run."""
+    G, R = 64 * 2 + 37, 4
+    spots = (0, 63, 64, G - 1)
+    rng = np.random.default_rng(97)
+    for row in top_rows():
+        name, D, kind, two = row
+        st, rs = random_state(rng, G, R)
+        for g in spots:
+            put_top_row(st, rs, g, row)
+        d = Dev(eng, st, rs)
+        for E in (4, 0):
+            want, wstats = rdm.ready(st, rs, ent_runs=E)
+            rd = filled_ready(eng, d.ps, G, E)
+            stats = eng.stats_buffer(DEV)
+            eng.ready(d.ps, d.fol, d.rs, rd, stats=stats)
+            assert records_of(rd) == (len(want), want), (name, E)
+            folded = host(eng.stats_reduce(stats))
+            for k, v in wstats.items():
+                assert int(folded[k]) == v & rdm.M64, (name, E, k)
+            recs = {r["group"] - GOFF: r for r in want}
+            for g in spots:
+                r = recs[g]
+                cnt, runs, cut_bit = ((r["ent_count"], r["ents"], rdm.ENTS_CUT) if kind == "ents"
+                                      else (r["apply_count"], r["apply"], rdm.APPLY_CUT))
+                assert cnt == (min(D, TOP) if E else D), (name, E)
+                assert bool(r["flags"] & cut_bit) == bool(E and D > TOP), (name, E)
+                assert sum(n for n, _ in runs) == (cnt if E else 0)
+                if E and D == TOP + 1 and not two:
+                    assert runs == [(0xFFFFFFFF, (1 << 32) + 3)] and cnt == 0xFFFFFFFF
+                    assert r["flags"] & cut_bit
 
 
 def test_rows_that_rule_out_the_pair_loads(eng):  # noqa: F811

@@ -16,6 +16,7 @@ import torch
 
 from etcd_amd import _lib
 from tests import follower_model as fm
+from tests import lift
 from tests import snapshot_model as sm
 from tests.test_gpu_progress import DEV, eng  # noqa: F401
 from tests.test_snapshot_model import compaction_cases, fixture_cases, storage, trace_cases
@@ -257,6 +258,60 @@ def test_random_differential(eng, S, R, lean):
     if not lean:
         want_c |= {sm.CP_CREATED, sm.CP_CREATED | sm.CP_COMPACTED, sm.CP_SNAP_OUT_OF_DATE}
     assert want_c <= seen_c, sorted(want_c - seen_c)
+
+
+@pytest.mark.parametrize("case", lift.SNAP_CASES, ids=str)
+def test_wide_differential(eng, case):
+    """Four rounds of qe_snapshot_step then qe_compact on one state whose
+    indexes and terms are lifted per group (tests/lift.py; `applied` with
+    them): both mask widths, the three run buckets, nine tiles and a ragged
+    one, statistics on, the model on the wide values.  Per index base every
+    answer of a MsgSnap and of a compaction is met (on the CPU in
+    tests/test_lift_model.py, and asserted here on what the device went
+    through)."""
+    S, R = case
+    box = {}
+
+    def harness(nodes):
+        if not box:
+            box["h"] = Harness(eng, nodes, R, S, stride=lift.G + lift.PAD, goff=lift.GOFF)
+        return box["h"]
+
+    def snapper(nodes, msgs):
+        outs = harness(nodes).snap(msgs)
+        return box["h"].nodes, outs
+
+    def compacter(nodes, reqs):
+        outs = harness(nodes).compact(reqs)
+        return box["h"].nodes, outs
+
+    ls, slog, clog = lift.snap_run(case, snapper, compacter)
+    lift.check_snap_coverage(ls, slog, clog)
+
+
+def test_top_of_range(eng):
+    """2^64 - 1 is QE_INDEX_INF and no log index: a MsgSnap there is
+    QE_SR_BAD_MSG, one at 2^64 - 2 restores with first_index = 2^64 - 1, a
+    compaction at a last index of 2^64 - 2 leaves first_index = 2^64 - 1 and
+    one at 2^64 - 1 is out of bound.  Each row of lift.snap_top_rows() at lane
+    0, 63, 64 and the last lane of a partial tile among random lifted
+    neighbours; the rows' literals hold the model."""
+    rng = np.random.default_rng(89)
+    R, S = 8, 3
+    for row in lift.snap_top_rows(S):
+        _, sn, msg, req, _ = row
+        nodes, msgs, reqs = lift.snap_neighbours(rng, G4, R, S)
+        for pos in SPOTS:
+            nodes[pos] = sn
+            if msg is not None:
+                msgs[pos] = msg
+            else:
+                reqs[pos] = req
+        h = Harness(eng, nodes, R, S, stride=G4 + 5, goff=1 << 33)
+        outs = h.snap(msgs) if msg is not None else h.compact(reqs)
+        for pos in SPOTS:
+            lift.check_snap_top_row(row, h.nodes[pos], outs[pos])
+        assert len({repr(sorted(outs[p].items())) for p in SPOTS}) == 1, row[0]
 
 
 def test_one_snapshot_in_a_sea_of_none(eng):

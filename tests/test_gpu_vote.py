@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from tests import follower_model as fm
+from tests import lift
 from tests import tick_model as tm
 from tests import vote_model as vm
 from tests import vote_traces as vt
@@ -275,6 +276,30 @@ def test_random_differential(eng, case):
     candidate's messages.  (That the run meets every result code is asserted
     on the CPU, tests/test_vote_model.py.)"""
     assert run_on_device(eng, case) == vm.random_run(case)
+
+
+@pytest.mark.parametrize("case", vm.RUN_CASES, ids=str)
+def test_wide_differential(eng, case):
+    """The eight run cases with every group's indexes and terms lifted
+    (tests/lift.py): the term preamble, isUpToDate's (lastTerm, lastIndex)
+    compare and term + 1 of a campaign on words whose high dword is live, that
+    cross 2^32 inside a log and that pass the int64 sign bit.  Nine tiles and a
+    ragged one, 8 calls, statistics on; the model runs on the wide values.
+    Per term base the run meets every result code tests/test_vote_model.py
+    proves for the small run (on the CPU in tests/test_lift_model.py, and
+    asserted here on what the device went through)."""
+    S, R, masks, flags, cand, have_self = case
+    box = {}
+
+    def stepper(nodes, msgs):
+        if not box:
+            box["h"] = Harness(eng, nodes, R, S, stride=lift.G + lift.PAD, flags=flags,
+                               goff=lift.GOFF, cand=cand, have_self=have_self)
+        outs = box["h"].step(msgs)
+        return box["h"].nodes, outs
+
+    ls, log = lift.vote_run(case, stepper)
+    lift.check_vote_coverage(case, ls, log)
 
 
 def test_tile_with_no_message(eng):
