@@ -402,6 +402,30 @@ class QeRequestsOut(C.Structure):
                 "group", "kind", "type", "to", "from_", "term", "index", "key", "src", "count")]
 
 
+# qe_apply_conf
+QE_AC_AUTO, QE_AC_JOINT_IMPLICIT, QE_AC_JOINT_EXPLICIT = 0, 1, 2   # ConfChangeTransition
+QE_AC_ANY_SLOT = 0xFF
+QE_AC_APPLIED, QE_AC_LEADER, QE_AC_DEFERRED = 1, 2, 3
+QE_AC_REFUSED = 16  # results >= this: nothing of the group written
+(QE_AC_BAD_GROUP, QE_AC_BAD_ORDER, QE_AC_BAD_CHANGE, QE_AC_CHANGER_ERROR,
+ QE_AC_SKIPPED) = range(16, 21)
+(QE_CC_OK, QE_CC_ERR_INVARIANT, QE_CC_ERR_ALREADY_JOINT, QE_CC_ERR_ZERO_VOTER_JOINT,
+ QE_CC_ERR_NOT_JOINT, QE_CC_ERR_SIMPLE_IN_JOINT, QE_CC_ERR_BAD_TYPE, QE_CC_ERR_REMOVED_ALL,
+ QE_CC_ERR_SIMPLE_MULTI, QE_CC_ERR_INVARIANT_OUT, QE_CC_ERR_NO_SLOT) = range(11)
+
+
+class QeApplyConfIn(C.Structure):
+    _fields_ = [("capacity", u64), ("n", u64), ("count", vp), ("max_changes", u32),
+                ("reserved", u32)] + [(k, vp) for k in (
+                    "group", "transition", "num_changes", "type", "node_id", "slot")]
+
+
+class QeApplyConfOut(C.Structure):
+    _fields_ = [(k, vp) for k in (
+        "result", "cc_result", "sw_result", "inc", "out", "learner", "learners_next", "tracked",
+        "new_progress", "auto_leave", "ids")]
+
+
 QE_BL_NONE, QE_BL_LEADER, QE_BL_NOT_MEMBER, QE_BL_RUNS_FULL = 0, 1, 2, 3
 QE_BL_BCAST = 1
 
@@ -505,6 +529,10 @@ PROTOTYPES = {
     "qe_requests_scratch_bytes": (C.c_size_t, [u64, u64]),
     "qe_requests": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeFollower),
                               C.POINTER(QeRequestsIn), C.POINTER(QeRequestsOut), vp, vp, vp]),
+    "qe_apply_conf_scratch_bytes": (C.c_size_t, [u64]),
+    "qe_apply_conf": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeFollower), C.POINTER(QeConf),
+                                C.POINTER(QeApplyConfIn), C.POINTER(QeApplyConfOut),
+                                C.POINTER(QeSwitch), vp, vp]),
     "qe_gen_groups": (C.c_int, [C.POINTER(QeGroups), C.POINTER(QeGenParams), vp]),
     "qe_apply_append_resps": (C.c_int, [u64, u32, u64, vp, vp, u64, vp, vp, vp, vp, vp]),
     "qe_pack_confstate": (C.c_int, [C.POINTER(QeConfStateCSR), u32, vp, vp, vp, vp, vp, vp]),

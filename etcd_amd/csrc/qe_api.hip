@@ -16,6 +16,7 @@
 #include "qe_ready.hpp"
 #include "qe_readstates.hpp"
 #include "qe_requests.hpp"
+#include "qe_applyconf.hpp"
 
 namespace qe {
 
@@ -1012,6 +1013,102 @@ int qe_confchange(const qe_conf *c, const qe_conf_changes *ch, const qe_progress
                        static_cast<hipStream_t>(stream), a);
     return hip_status(hipGetLastError());
   });
+}
+
+// qe_apply_conf's scratch: the `switched` row, then the switch kernel's result
+// row for a call without sw, each padded to 16 B.
+static size_t apply_conf_row_bytes(uint64_t num_groups) {
+  return (static_cast<size_t>(num_groups) + 15) & ~static_cast<size_t>(15);
+}
+
+size_t qe_apply_conf_scratch_bytes(uint64_t num_groups) {
+  return 2 * apply_conf_row_bytes(num_groups);
+}
+
+int qe_apply_conf(const qe_progress *p, const qe_follower *f, const qe_conf *c,
+                  const qe_apply_conf_in *in, const qe_apply_conf_out *out, const qe_switch *sw,
+                  void *scratch, void *stream) {
+  PArgs pa;
+  const int rc = progress_args(p, pa);  // the switch kernel's own checks
+  if (rc) return rc;
+  if (!f || !c || !in || !out) return QE_EINVAL;
+  if (!f->state || !p->inc_mask || !p->out_mask || !p->tracked || !p->self_slot) return QE_EINVAL;
+  if (conf_mismatch(p, c)) return QE_EINVAL;
+  if (!c->slot_ids || !c->inc_mask || !c->out_mask || !c->learner_mask ||
+      !c->learners_next_mask || !c->is_learner || !c->tracked || !c->auto_leave)
+    return QE_EINVAL;
+  if (in->reserved || in->max_changes > 255) return QE_EINVAL;
+  if (in->capacity && (!in->group || !in->transition || !in->num_changes ||
+                       (in->max_changes && (!in->type || !in->node_id))))
+    return QE_EINVAL;
+  if (in->capacity && (!out->result || !out->cc_result || !out->sw_result || !out->inc ||
+                       !out->out || !out->learner || !out->learners_next || !out->tracked ||
+                       !out->new_progress || !out->auto_leave))
+    return QE_EINVAL;
+  if (sw && (!sw->result || sw->bytes_requested)) return QE_EINVAL;
+  if (!scratch || !al(scratch, 16)) return QE_EINVAL;
+  if (p->num_groups == 0 || in->capacity == 0) return QE_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const size_t row = apply_conf_row_bytes(p->num_groups);
+  uint8_t *switched = static_cast<uint8_t *>(scratch);
+  uint8_t *swres = sw ? sw->result : switched + row;
+  ACArgs a{};
+  a.G = p->num_groups;
+  a.goff = p->group_offset;
+  a.pstride = p->stride;
+  a.cap = in->capacity;
+  a.n = in->n < in->capacity ? in->n : in->capacity;
+  a.count = in->count;
+  a.C = in->max_changes;
+  a.ids = c->slot_ids;
+  a.inc = c->inc_mask;
+  a.out = c->out_mask;
+  a.lrn = c->learner_mask;
+  a.lnx = c->learners_next_mask;
+  a.isl = c->is_learner;
+  a.trk = c->tracked;
+  a.auto_leave = c->auto_leave;
+  // p's rows of the configuration, where they are not c's own
+  a.p_inc = p->inc_mask != c->inc_mask ? const_cast<void *>(p->inc_mask) : nullptr;
+  a.p_out = p->out_mask != c->out_mask ? const_cast<void *>(p->out_mask) : nullptr;
+  a.p_trk = p->tracked != c->tracked ? const_cast<void *>(p->tracked) : nullptr;
+  a.p_match = p->match;
+  a.p_next = p->next;
+  a.p_pending = p->pending_snapshot;
+  a.p_pw = p->peer;
+  a.last_index = p->last_index;
+  a.fstate = f->state;
+  a.group = in->group;
+  a.transition = in->transition;
+  a.nchanges = in->num_changes;
+  a.type = in->type;
+  a.node = in->node_id;
+  a.slot = in->slot;
+  a.result = out->result;
+  a.cc_result = out->cc_result;
+  a.sw_result = out->sw_result;
+  a.o_inc = out->inc;
+  a.o_out = out->out;
+  a.o_lrn = out->learner;
+  a.o_lnx = out->learners_next;
+  a.o_trk = out->tracked;
+  a.o_newp = out->new_progress;
+  a.o_al = out->auto_leave;
+  a.o_ids = out->ids;
+  a.switched = switched;
+  a.swres = swres;
+  int s = dispatch_apply_conf_clear(switched, row, st);
+  if (s) return s;
+  s = dispatch_apply_conf(a, p->num_slots, st);
+  if (s) return s;
+  // switchToConfig's leader half, by qe_switch_config's kernel and dispatch
+  pa.sw_switched = switched;
+  pa.sw_result = swres;
+  pa.sent = sw ? sw->sent : nullptr;
+  pa.snap = sw ? sw->snap : nullptr;
+  s = launch_progress(p, pa, ProgressOp::SwitchConfig, false, stream);
+  if (s) return s;
+  return dispatch_apply_conf_gather(a, st);
 }
 
 size_t qe_collect_scratch_bytes(uint64_t num_groups) {

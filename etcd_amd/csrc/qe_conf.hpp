@@ -70,11 +70,21 @@ __device__ __forceinline__ uint32_t cc_find(const uint64_t (&id)[kCCMax], uint32
   return m & (0u - m);
 }
 
-// initProgress (:251-274): the lowest untracked slot gets the peer.
-template <int S>
+// The slot a change that creates a Progress names: kCCAnySlot = the lowest
+// untracked one (qe_confchange's rule).
+constexpr uint32_t kCCAnySlot = 0xFFu;
+
+// initProgress (:251-274): the lowest untracked slot gets the peer; with
+// NAMED (qe_apply_conf) the slot `want` when that is untracked, unless want is
+// kCCAnySlot.  (A compile-time switch: as a run-time one it costs k_confchange
+// 12 VGPRs at 9 slots and above.)
+template <int S, bool NAMED = false>
 __device__ __forceinline__ int cc_init(CCState &c, uint64_t (&id)[kCCMax], uint64_t node,
-                                       bool learner) {
-  const uint32_t free = ~c.trk & ((1u << S) - 1u);
+                                       bool learner, uint32_t want = kCCAnySlot) {
+  uint32_t free = ~c.trk & ((1u << S) - 1u);
+  if constexpr (NAMED) {
+    if (want != kCCAnySlot) free &= want < static_cast<uint32_t>(S) ? (1u << want) : 0u;
+  }
   if (free == 0) return QE_CC_ERR_NO_SLOT;
   const uint32_t b = free & (0u - free);
 #pragma unroll
@@ -172,53 +182,146 @@ __device__ __forceinline__ void cc_issue(const CCArgs &a, uint64_t t, uint32_t l
   x.li = bld64(mk_rsrc(a.last_index + g0, a.p_match ? n * 8 : 0u), act ? lane * 8 : kOOB);
 }
 
-// apply (:152-177): change k is (node[k], type[k]); the first kCCPre come
-// from the tile's registers, later ones are loaded here.
+// One ConfChangeSingle of apply (:152-177): (node, typ), a created Progress in
+// the slot `want`.  Left to the inliner, as the lambda it was in cc_apply: it
+// is simplified on its own first, and k_confchange keeps its registers.
+template <int S, bool NAMED = false>
+__device__ inline int cc_one(CCState &c, uint64_t (&id)[kCCMax], uint64_t node, uint32_t typ,
+                             uint32_t want = kCCAnySlot) {
+  if (node == 0) return QE_CC_OK;  // etcd's "do not apply" marker (:154-160)
+  const uint32_t b = cc_find<S>(id, c.trk, node);
+  if (typ == QE_CC_ADD_NODE) {  // makeVoter (:181-193)
+    if (b == 0) return cc_init<S, NAMED>(c, id, node, false, want);
+    c.isl &= ~b;
+    c.lrn &= ~b;
+    c.lnx &= ~b;
+    c.inc |= b;
+  } else if (typ == QE_CC_ADD_LEARNER_NODE) {  // makeLearner (:207-231)
+    if (b == 0) return cc_init<S, NAMED>(c, id, node, true, want);
+    if ((c.isl & b) == 0) {
+      // remove(), but the Progress is put back (prs[id] = pr)
+      c.inc &= ~b;
+      c.lrn &= ~b;
+      c.lnx &= ~b;
+      if (c.out & b) {
+        c.lnx |= b;
+      } else {
+        c.isl |= b;
+        c.lrn |= b;
+      }
+    }
+  } else if (typ == QE_CC_REMOVE_NODE) {
+    if (b) cc_remove(c, b);
+  } else if (typ != QE_CC_UPDATE_NODE) {
+    return QE_CC_ERR_BAD_TYPE;
+  }
+  return QE_CC_OK;
+}
+
+// apply (:152-177) for qe_confchange: change k is (node[k], type[k]); the
+// first kCCPre come from the tile's registers, later ones are loaded here.
 template <int S>
 __device__ __forceinline__ int cc_apply(const CCArgs &a, uint64_t g, uint32_t count,
                                         const CCTile<S> &x, CCState &c, uint64_t (&id)[kCCMax]) {
   const uint32_t n = count < a.C ? count : a.C;
-  auto one = [&](uint64_t node, uint32_t typ) -> int {
-    if (node == 0) return QE_CC_OK;  // etcd's "do not apply" marker (:154-160)
-    const uint32_t b = cc_find<S>(id, c.trk, node);
-    if (typ == QE_CC_ADD_NODE) {  // makeVoter (:181-193)
-      if (b == 0) return cc_init<S>(c, id, node, false);
-      c.isl &= ~b;
-      c.lrn &= ~b;
-      c.lnx &= ~b;
-      c.inc |= b;
-    } else if (typ == QE_CC_ADD_LEARNER_NODE) {  // makeLearner (:207-231)
-      if (b == 0) return cc_init<S>(c, id, node, true);
-      if ((c.isl & b) == 0) {
-        // remove(), but the Progress is put back (prs[id] = pr)
-        c.inc &= ~b;
-        c.lrn &= ~b;
-        c.lnx &= ~b;
-        if (c.out & b) {
-          c.lnx |= b;
-        } else {
-          c.isl |= b;
-          c.lrn |= b;
-        }
-      }
-    } else if (typ == QE_CC_REMOVE_NODE) {
-      if (b) cc_remove(c, b);
-    } else if (typ != QE_CC_UPDATE_NODE) {
-      return QE_CC_ERR_BAD_TYPE;
-    }
-    return QE_CC_OK;
-  };
 #pragma unroll
   for (int j = 0; j < kCCPre; j++) {
     if (static_cast<uint32_t>(j) >= n) break;
-    const int rc = one(x.node[j], x.typ[j]);
+    const int rc = cc_one<S>(c, id, x.node[j], x.typ[j]);
     if (rc) return rc;
   }
   for (uint32_t k = kCCPre; k < n; k++) {
-    const int rc = one(a.node[k * a.stride + g], a.type[k * a.stride + g]);
+    const int rc = cc_one<S>(c, id, a.node[k * a.stride + g], a.type[k * a.stride + g]);
     if (rc) return rc;
   }
   return c.inc == 0 ? QE_CC_ERR_REMOVED_ALL : QE_CC_OK;
+}
+
+// symdiff (:384-401): how many ids are an incoming voter before the operation
+// or after it, but not both.
+template <int S>
+__device__ __forceinline__ uint32_t cc_symdiff(uint32_t inc0, uint32_t inc,
+                                               const uint64_t (&id0)[kCCMax],
+                                               const uint64_t (&id)[kCCMax]) {
+  uint32_t diff = 0;
+#pragma unroll
+  for (int s = 0; s < S; s++) {
+    bool in_new = false, in_old = false;
+#pragma unroll
+    for (int u = 0; u < S; u++) {
+      in_new |= ((inc >> u) & 1u) && id[u] == id0[s];
+      in_old |= ((inc0 >> u) & 1u) && id0[u] == id[s];
+    }
+    diff += (((inc0 >> s) & 1u) && !in_new) ? 1u : 0u;
+    diff += (((inc >> s) & 1u) && !in_old) ? 1u : 0u;
+  }
+  return diff;
+}
+
+// LeaveJoint's body (:99-122) on a joint configuration.
+__device__ __forceinline__ void cc_leave(CCState &c) {
+  c.lrn |= c.lnx;
+  c.isl |= c.lnx;
+  c.lnx = 0;
+  const uint32_t dead = c.out & ~c.inc & ~c.lrn;
+  c.trk &= ~dead;
+  c.isl &= ~dead;
+  c.out = 0;
+  c.al = 0;
+}
+
+// Changer.Simple / EnterJoint / LeaveJoint (:49-147) on one group's state
+// for a caller that keeps the changes elsewhere than a CCTile (qe_apply_conf):
+// checkInvariants before and after, and `apply(c, id)` -> QE_CC_* runs the
+// operation's changes.  On an error c and id are whatever the failed operation
+// left: the caller keeps the state it had.
+//
+// cc_finish below holds the same branch skeleton written out; the bodies
+// that are more than a line (the single changes, the invariants, the symmetric
+// difference, LeaveJoint) are shared functions.  Calling this whole function
+// from cc_finish, in any of the forms tried (a lambda, a functor with an
+// inlined call operator, this function left to the inliner, the IDs' copy
+// passed in), costs k_confchange 12 VGPRs at 3 slots and 13 at 5 (116 -> 129:
+// three waves per SIMD instead of four), so the skeleton stays in two places.
+// With cc_symdiff and cc_leave shared k_confchange keeps its VGPRs (106 / 116 /
+// 134 / 191 at 3 / 5 / 9 / 16 slots; 192 before at 16) and its occupancy; the
+// SGPRs it parks in VGPR lanes move (66 / 85 / 237 / 1665 before, 69 / 169 /
+// 239 / 1565 now), still without scratch memory.
+template <int S, class Apply>
+__device__ __forceinline__ int cc_change(uint32_t op, CCState &c, uint64_t (&id)[kCCMax],
+                                         Apply &&apply) {
+  uint64_t id0[kCCMax];
+#pragma unroll
+  for (int s = 0; s < kCCMax; s++) id0[s] = id[s];
+  const uint32_t inc0 = c.inc;
+  int rc = cc_invariants<S>(c, id) ? QE_CC_OK : QE_CC_ERR_INVARIANT;  // checkAndCopy
+  if (rc == QE_CC_OK) {
+    if (op == QE_CC_OP_SIMPLE) {  // :130-147
+      if (c.out) rc = QE_CC_ERR_SIMPLE_IN_JOINT;
+      if (rc == QE_CC_OK) rc = apply(c, id);
+      if (rc == QE_CC_OK) {
+        if (cc_symdiff<S>(inc0, c.inc, id0, id) > 1) rc = QE_CC_ERR_SIMPLE_MULTI;
+      }
+    } else if (op == QE_CC_OP_ENTER_JOINT || op == QE_CC_OP_ENTER_JOINT_AUTO) {  // :49-76
+      if (c.out) rc = QE_CC_ERR_ALREADY_JOINT;
+      else if (c.inc == 0) rc = QE_CC_ERR_ZERO_VOTER_JOINT;
+      if (rc == QE_CC_OK) {
+        c.out = c.inc;
+        rc = apply(c, id);
+        c.al = op == QE_CC_OP_ENTER_JOINT_AUTO ? 1u : 0u;
+      }
+    } else if (op == QE_CC_OP_LEAVE_JOINT) {  // :92-123
+      if (c.out == 0) {
+        rc = QE_CC_ERR_NOT_JOINT;
+      } else {
+        cc_leave(c);
+      }
+    } else {
+      rc = QE_CC_ERR_BAD_TYPE;
+    }
+    if (rc == QE_CC_OK && !cc_invariants<S>(c, id)) rc = QE_CC_ERR_INVARIANT_OUT;
+  }
+  return rc;
 }
 
 // One tile's change (a group per lane) and its stores: the result and
@@ -253,20 +356,7 @@ __device__ __forceinline__ void cc_finish(const CCArgs &a, uint64_t t, uint32_t 
         if (c.out) rc = QE_CC_ERR_SIMPLE_IN_JOINT;
         if (rc == QE_CC_OK) rc = cc_apply<S>(a, g0 + lane, cc_count(h), x, c, id);
         if (rc == QE_CC_OK) {
-          // symdiff of the incoming voter ids (:384-401)
-          uint32_t diff = 0;
-#pragma unroll
-          for (int s = 0; s < S; s++) {
-            bool in_new = false, in_old = false;
-#pragma unroll
-            for (int u = 0; u < S; u++) {
-              in_new |= ((c.inc >> u) & 1u) && id[u] == id0[s];
-              in_old |= ((inc0 >> u) & 1u) && id0[u] == id[s];
-            }
-            diff += (((inc0 >> s) & 1u) && !in_new) ? 1u : 0u;
-            diff += (((c.inc >> s) & 1u) && !in_old) ? 1u : 0u;
-          }
-          if (diff > 1) rc = QE_CC_ERR_SIMPLE_MULTI;
+          if (cc_symdiff<S>(inc0, c.inc, id0, id) > 1) rc = QE_CC_ERR_SIMPLE_MULTI;
         }
       } else if (op == QE_CC_OP_ENTER_JOINT || op == QE_CC_OP_ENTER_JOINT_AUTO) {  // :49-76
         if (c.out) rc = QE_CC_ERR_ALREADY_JOINT;
@@ -280,14 +370,7 @@ __device__ __forceinline__ void cc_finish(const CCArgs &a, uint64_t t, uint32_t 
         if (c.out == 0) {
           rc = QE_CC_ERR_NOT_JOINT;
         } else {
-          c.lrn |= c.lnx;
-          c.isl |= c.lnx;
-          c.lnx = 0;
-          const uint32_t dead = c.out & ~c.inc & ~c.lrn;
-          c.trk &= ~dead;
-          c.isl &= ~dead;
-          c.out = 0;
-          c.al = 0;
+          cc_leave(c);
         }
       } else {
         rc = QE_CC_ERR_BAD_TYPE;

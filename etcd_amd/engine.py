@@ -1871,3 +1871,119 @@ def confchange(cs, ch, ps=None):
     p = C.byref(ps.struct()) if ps is not None else None
     check("qe_confchange", _lib.lib().qe_confchange(C.byref(c), C.byref(x), p,
                                                      _stream(cs.device)))
+
+
+class ApplyConf(_Records):
+    """The record list of qe_apply_conf (qe_apply_conf_in) for up to `capacity`
+    committed conf-change entries and its per-record outputs
+    (qe_apply_conf_out).  The list rows are q_group int64 storage of the u64
+    field, q_transition (QE_AC_AUTO ...) / q_num_changes u8 and, laid out
+    [max_changes][capacity], q_type u8 (QE_CC_ADD_NODE ...), q_node_id int64 and
+    with slots=True q_slot u8 (QE_AC_ANY_SLOT = the lowest untracked slot).
+    Per record: result (QE_AC_*), cc_result (QE_CC_*), sw_result (QE_SW_*) u8,
+    the ConfState after the record as slot masks inc / out / learner /
+    learners_next / tracked / new_progress and auto_leave u8, and with ids=True
+    the tracked slots' ids [S][capacity].  `count` (int64[1]) is the device
+    count qe_apply_conf reads with device_count=True; load_host sets it.  The
+    scratch of the call is cached here."""
+
+    FIELDS = ("result:u8 cc_result:u8 sw_result:u8 inc:mask out:mask learner:mask "
+              "learners_next:mask tracked:mask new_progress:mask auto_leave:u8 ids:u64? count:u64")
+    RUNS = ("ids",)
+    LIST = {"group": "u64", "transition": "u8", "num_changes": "u8"}
+    CHANGES = {"type": "u8", "node_id": "u64", "slot": "u8"}
+
+    def __init__(self, ps, capacity, max_changes=1, slots=True, ids=True, device_count=False):
+        if not 0 <= int(max_changes) <= 255:
+            raise ValueError("max_changes must be 0..255")
+        dev = ps.device
+        self.S, self.max_changes, self.n = ps.S, int(max_changes), 0
+        self.device_count = bool(device_count)
+        self.capacity = int(capacity)
+        c = max(1, self.capacity)
+        md = mask_torch_dtype(ps.S)
+        for k in self.ARRAYS:
+            kind = self.KIND[k]
+            size = 1 if k == "count" else ps.S * c if k == "ids" else c
+            t = None if (k == "ids" and not ids) else torch.zeros(
+                size, dtype=md if kind == "mask" else _TORCH[kind], device=dev)
+            setattr(self, k, t)
+        for k, kind in self.LIST.items():
+            setattr(self, "q_" + k, torch.zeros(c, dtype=_TORCH[kind], device=dev))
+        for k, kind in self.CHANGES.items():
+            setattr(self, "q_" + k, None if (k == "slot" and not slots) else
+                    torch.zeros(max(1, self.max_changes) * c, dtype=_TORCH[kind], device=dev))
+        self.scratch = None
+
+    def load_host(self, **arrays):
+        """The list from numpy arrays of the unsigned types, replacing the one
+        loaded before: group / transition / num_changes [m], type / node_id /
+        slot [max_changes][m] for the m records given.  A field left out is 0
+        (slot: QE_AC_ANY_SLOT).  m may exceed the capacity: the rows then hold
+        the first `capacity` records and qe_apply_conf sees n = m."""
+        for k in arrays:
+            if k not in self.LIST and k not in self.CHANGES:
+                raise KeyError(k)
+        m = len(arrays["group"])
+        keep, cap = min(m, self.capacity), max(1, self.capacity)
+        for k in list(self.LIST) + list(self.CHANGES):
+            dst = getattr(self, "q_" + k)
+            if dst is None:
+                continue
+            rows = self.max_changes if k in self.CHANGES else 1
+            if not rows:
+                continue
+            dst.fill_(_lib.QE_AC_ANY_SLOT if k == "slot" else 0)
+            if k not in arrays or not keep:
+                continue
+            a = np.ascontiguousarray(arrays[k])
+            a = a.view(_SIGNED.get(a.dtype, a.dtype)).reshape(rows, m)[:, :keep]
+            dst.view(-1, cap)[:rows, :keep].copy_(torch.from_numpy(a.copy()).to(dst.device))
+        self.n = m
+        self.count.fill_(m)
+        return self
+
+    def records(self):
+        """-> (n, the per-record outputs cut to min(n, capacity) as numpy
+        arrays; ids as [S][n], None when left out)."""
+        n, cap = min(self.n, self.capacity), max(1, self.capacity)
+        out = {}
+        for k, a in self.host().items():
+            if k == "count":
+                continue
+            out[k] = None if a is None else a.reshape(-1, cap)[:, :n] if k in self.RUNS else a[:n]
+        return self.n, out
+
+    def results(self):
+        """-> (result, cc_result, sw_result) of the min(n, capacity) records."""
+        n = min(self.n, self.capacity)
+        return tuple(getattr(self, k)[:n].cpu().numpy() for k in ("result", "cc_result", "sw_result"))
+
+    def struct_in(self):
+        return _lib.QeApplyConfIn(
+            self.capacity, self.n, _ptr(self.count) if self.device_count else None,
+            self.max_changes, 0, _ptr(self.q_group), _ptr(self.q_transition),
+            _ptr(self.q_num_changes), _ptr(self.q_type), _ptr(self.q_node_id), _ptr(self.q_slot))
+
+    def struct_out(self):
+        return _lib.QeApplyConfOut(*[_ptr(getattr(self, k)) for k in self.ARRAYS if k != "count"])
+
+
+def apply_conf(ps, fol, conf, ac, sw=None):
+    """qe_apply_conf: the committed conf-change entries listed in `ac` applied
+    as RawNode.ApplyConfChange does, on every role: the ConfChangeV2 decoded
+    and the Changer run on `conf` (and on ps's inc / out / tracked where those
+    are other tensors), initProgress for the created slots, and for the groups
+    that lead switchToConfig's leader half (qe_switch_config's kernel) on a
+    `switched` row the call keeps in its scratch.  With a Switch `sw` its
+    result / sent / snap rows are filled for qe_outbox.  The per-record results
+    and ConfStates are left in `ac`."""
+    lib = _lib.lib()
+    _scratch(ac, ps.device, lib.qe_apply_conf_scratch_bytes(ps.G) + 16)
+    base = ac.scratch.data_ptr()
+    p, f, c, i, o = ps.struct(), fol.struct(), conf.struct(), ac.struct_in(), ac.struct_out()
+    q = C.byref(sw.struct()) if sw is not None else None
+    check("qe_apply_conf", lib.qe_apply_conf(C.byref(p), C.byref(f), C.byref(c), C.byref(i),
+                                             C.byref(o), q, (base + 15) & ~15,
+                                             _stream(ps.device)))
+    return ac

@@ -2650,6 +2650,151 @@ size_t qe_requests_scratch_bytes(uint64_t num_groups, uint64_t num_records);
 int qe_requests(const qe_progress *p, const qe_follower *f, const qe_requests_in *in,
                 const qe_requests_out *out, void *scratch, uint64_t *stats, void *stream);
 
+/* qe_apply_conf (additive in ABI 8): committed conf-change entries applied as a
+ * device list, on every role -- RawNode.ApplyConfChange -> raft.applyConfChange
+ * -> switchToConfig (raft/rawnode.go:104-107, raft/raft.go:1623-1700).  A host
+ * lists the ConfChangeV2 entries a Ready handed it to apply (a V1 ConfChange as
+ * its AsV2 form: QE_AC_AUTO with one change) and gets back, per record, what
+ * happened and the ConfState ApplyConfChange returns.  It builds no [G] row
+ * (op, count, last_index, switched) and reads none (state, the masks).
+ *
+ * The list: n records, n = min(*in->count, capacity) when in->count (DEVICE) is
+ * given, else min(in->n, capacity), as qe_advance reads its list.  Record i:
+ *   group[i]          absolute; g = group[i] - p->group_offset
+ *   transition[i]     QE_AC_AUTO, QE_AC_JOINT_IMPLICIT, QE_AC_JOINT_EXPLICIT
+ *                     (ConfChangeTransition, raft/raftpb/raft.pb.go)
+ *   num_changes[i]    its ConfChangeSingle entries, <= max_changes (C)
+ *   type[k*capacity+i], node_id[k*capacity+i]   change k (QE_CC_ADD_NODE ...;
+ *                     node 0 = ignored, as qe_confchange)
+ *   slot[k*capacity+i]   optional row: the slot a change that creates a
+ *                     Progress must take; QE_AC_ANY_SLOT (0xFF), or a NULL
+ *                     row, is qe_confchange's rule, the lowest untracked slot.
+ *                     A named slot that is tracked or >= num_slots makes the
+ *                     change fail with QE_CC_ERR_NO_SLOT.  A host that keeps
+ *                     slot = node (the layout qe_outbox / qe_inbox / qe_replies
+ *                     route by) names the slot of every added id.
+ * The records are in non-decreasing group order; the records of one group are
+ * a run of neighbours, applied in list order.
+ *
+ * Per record, result[i] (QE_AC_*), cc_result[i] (QE_CC_*), sw_result[i]
+ * (QE_SW_*):
+ *  1. Decode (raft/raftpb/confchange.go:71-107).  num_changes == 0 and
+ *     transition == QE_AC_AUTO: LeaveJoint.  Else transition != QE_AC_AUTO or
+ *     num_changes > 1: EnterJoint with autoLeave = transition !=
+ *     QE_AC_JOINT_EXPLICIT.  Else Simple.
+ *  2. Changer (raft/confchange/confchange.go:49-274) with LastIndex =
+ *     p->last_index[g], on the rows of c, exactly as qe_confchange runs it: on
+ *     success only the words of c that changed are written (a created slot's
+ *     id, 0 for a slot that lost its Progress), the created slots' Progress in
+ *     p is initialised (Match 0, Next = last_index, StateProbe, RecentActive,
+ *     no pending snapshot) and cc_result = QE_CC_OK.  p->inc_mask / out_mask /
+ *     tracked are switchToConfig's view of the new configuration.  ALIASING:
+ *     each of the three is either the very pointer of c's inc_mask / out_mask /
+ *     tracked (one row serves both; the usual set-up) or memory that overlaps
+ *     no row of c, and is then written too (all three words of the group, on
+ *     every applied record).  No other row of c, p, f, in, out or scratch may
+ *     overlap another.
+ *  3. Role.  f->state[g] != QE_STATE_LEADER: switchToConfig returns at :1678,
+ *     result = QE_AC_APPLIED, sw_result = QE_SW_NONE.  A leader: result =
+ *     QE_AC_LEADER and sw_result is the QE_SW_* byte (QE_SW_TRANSFER_ABORTED
+ *     included) of switchToConfig's leader half, which qe_switch_config's
+ *     kernel runs after the list on the groups this call marked in scratch;
+ *     p->self_slot tells it whether the leader still has a Progress
+ *     (QE_SW_REMOVED).  sw->result / sent / snap ([G], device) are filled for
+ *     every group as qe_switch_config fills them (0 for a group not switched),
+ *     so qe_outbox consumes sent / snap unchanged; sw->switched is not read.
+ *     State, stores and result bytes of the leader half are those of
+ *     qe_confchange followed by qe_switch_config on the same state.
+ *  4. Several records of one group.  A group that does not lead applies them
+ *     all, in list order, each on the configuration its predecessor left.  A
+ *     leader applies the first; each later one is QE_AC_DEFERRED and nothing is
+ *     done for it (the sends of the first are harvested with qe_outbox first,
+ *     then the host lists the deferred records again).
+ *  5. Refusals, result >= QE_AC_REFUSED: nothing of the group is written by
+ *     the record.
+ *       QE_AC_BAD_GROUP      g outside [0, num_groups)
+ *       QE_AC_BAD_ORDER      group[i] < group[i-1].  (A list out of order may
+ *                            name a group in two runs; what those runs leave
+ *                            of it is unspecified, memory stays in bounds.)
+ *       QE_AC_BAD_CHANGE     transition > 2 or num_changes > max_changes
+ *       QE_AC_CHANGER_ERROR  the Changer refused: the reference's panic
+ *                            (:1637-1640); cc_result = the QE_CC_ERR_*
+ *       QE_AC_SKIPPED        an earlier record of the run was refused
+ *     A refusal ends its run: every later record of the group is SKIPPED.
+ *  6. The ConfState (ProgressTracker.ConfState, tracker.go:146-154) after the
+ *     record, in slot form: inc (Voters), out (VotersOutgoing), learner,
+ *     learners_next, tracked (mask-typed), auto_leave, new_progress (the slots
+ *     whose Progress this record created), and with ids ([S][capacity]) the id
+ *     of every tracked slot, 0 elsewhere.  A DEFERRED, SKIPPED, BAD_CHANGE or
+ *     CHANGER_ERROR record shows the configuration as it stands; a record of a
+ *     BAD_GROUP or BAD_ORDER run shows zeros.  Nothing at or past n is touched
+ *     in any output array.
+ * scratch: qe_apply_conf_scratch_bytes(num_groups) bytes of device memory,
+ * 16-B aligned, owned by the call: it clears what it needs (the `switched`
+ * row, G bytes) itself, so calls follow each other on one stream with no host
+ * work between them.  Stream-ordered, four kernels (clear, the list, the
+ * switch kernel over the batch, the gather of sw_result), no host
+ * synchronisation.  Of p the list kernel reads num_groups, group_offset,
+ * num_slots, stride, last_index and writes match / next / pending_snapshot /
+ * peer of the created slots; the switch kernel reads and writes what
+ * qe_switch_config does.
+ * QE_EINVAL: a NULL p / f / c / in / out / scratch; whatever qe_switch_config
+ * refuses in p (its QE_ERANGE cases stay QE_ERANGE); a NULL f->state; a NULL
+ * p->inc_mask / out_mask / tracked / self_slot; c->num_groups or num_slots
+ * other than p's, a nonzero c->reserved, a NULL row of c; a nonzero
+ * in->reserved, max_changes > 255; capacity > 0 with a NULL group / transition
+ * / num_changes, or with max_changes > 0 and a NULL type / node_id; capacity >
+ * 0 with a NULL result / cc_result / sw_result / inc / out / learner /
+ * learners_next / tracked / new_progress / auto_leave (ids may be NULL); sw
+ * with a NULL result or a non-NULL bytes_requested; scratch not 16-B aligned.
+ * Every argument check runs before the first HIP call.  capacity == 0 or
+ * num_groups == 0 is QE_OK: nothing is written. */
+#define QE_AC_AUTO 0              /* ConfChangeTransitionAuto */
+#define QE_AC_JOINT_IMPLICIT 1    /* ConfChangeTransitionJointImplicit */
+#define QE_AC_JOINT_EXPLICIT 2    /* ConfChangeTransitionJointExplicit */
+#define QE_AC_ANY_SLOT 0xFFu      /* slot: the lowest untracked one */
+#define QE_AC_APPLIED 1           /* applied; the group does not lead */
+#define QE_AC_LEADER 2            /* applied by a leader: sw_result holds the QE_SW_* */
+#define QE_AC_DEFERRED 3          /* a leader's later record: list it again */
+#define QE_AC_REFUSED 16          /* results >= this: nothing of the group written */
+#define QE_AC_BAD_GROUP 16
+#define QE_AC_BAD_ORDER 17
+#define QE_AC_BAD_CHANGE 18
+#define QE_AC_CHANGER_ERROR 19
+#define QE_AC_SKIPPED 20
+
+typedef struct qe_apply_conf_in {
+  uint64_t capacity;            /* records the arrays of in and out hold */
+  uint64_t n;                   /* records listed (read when count is NULL) */
+  const uint64_t *count;        /* device, or NULL: records listed */
+  uint32_t max_changes;         /* C, changes per record at most, <= 255 */
+  uint32_t reserved;            /* must be 0 */
+  const uint64_t *group;        /* [capacity] */
+  const uint8_t  *transition;   /* [capacity] QE_AC_AUTO ... */
+  const uint8_t  *num_changes;  /* [capacity] */
+  const uint8_t  *type;         /* [C][capacity] QE_CC_ADD_NODE ... */
+  const uint64_t *node_id;      /* [C][capacity] */
+  const uint8_t  *slot;         /* [C][capacity] or NULL */
+} qe_apply_conf_in;
+
+typedef struct qe_apply_conf_out {
+  uint8_t *result;              /* [capacity] QE_AC_* */
+  uint8_t *cc_result;           /* [capacity] QE_CC_* */
+  uint8_t *sw_result;           /* [capacity] QE_SW_* */
+  void *inc, *out;              /* [capacity] mask-typed: Voters, VotersOutgoing */
+  void *learner, *learners_next; /* [capacity] mask-typed */
+  void *tracked;                /* [capacity] mask-typed */
+  void *new_progress;           /* [capacity] mask-typed */
+  uint8_t *auto_leave;          /* [capacity] */
+  uint64_t *ids;                /* [S][capacity] or NULL */
+} qe_apply_conf_out;
+
+size_t qe_apply_conf_scratch_bytes(uint64_t num_groups);
+/* sw may be NULL (the [G] rows of the leader half are not wanted). */
+int qe_apply_conf(const qe_progress *p, const qe_follower *f, const qe_conf *c,
+                  const qe_apply_conf_in *in, const qe_apply_conf_out *out,
+                  const qe_switch *sw, void *scratch, void *stream);
+
 /* ---- statistics -------------------------------------------------------- */
 
 /* out[QE_STATS_COUNTERS] (device) = sum over shards of stats (device). */
