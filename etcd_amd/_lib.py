@@ -310,6 +310,36 @@ class QeRepliesOut(C.Structure):
         "group", "to", "type", "term", "index", "log_term", "hint", "ctx", "flags", "count")]
 
 
+# qe_carry
+QE_PEER_NONE = 0xFFFFFFFFFFFFFFFF
+QE_CARRY_SNAP_STATUS = 1
+QE_CARRY_TYPES = 0xFC7E        # the carriable types 1..6 and 10..15, as `ignore` bits
+QE_TD_LOCAL, QE_TD_REMOTE, QE_TD_LOST = 1, 2, 3
+QE_TD_BAD = 255
+QE_STAT_CARRY_BAD = 1          # = QE_STAT_COMMIT_INF
+QE_STAT_CARRY_LOCAL, QE_STAT_CARRY_LOST, QE_STAT_CARRY_REMOTE = 4, 5, 6   # = QE_STAT_VOTE_*
+QE_STAT_CARRY_SNAP_STATUS = 9  # = QE_STAT_COMMIT_ADVANCED
+
+
+class QePeers(C.Structure):
+    _fields_ = [("peer_group", vp), ("peer_from", vp)]
+
+
+class QeCarryIn(C.Structure):
+    _fields_ = [("capacity", u64), ("count", vp), ("msg_runs", u32), ("flags", u32)] + [
+        (k, vp) for k in ("group", "to", "type", "term", "index", "log_term", "commit", "hint",
+                          "ctx", "mflags", "ent_len", "ent_term", "drop", "cut")] + [
+        ("ignore", u32), ("reserved", u32)]
+
+
+class QeCarryOut(C.Structure):
+    _fields_ = [("capacity", u64), ("base", u64), ("ent_pitch", u64), ("msg_runs", u32),
+                ("reserved", u32)] + [(k, vp) for k in (
+                    "group", "from_", "type", "term", "index", "log_term", "commit", "hint", "ctx",
+                    "mflags", "ent_len", "ent_term", "src", "count", "disposition", "remote",
+                    "remote_count")]
+
+
 # qe_ready_note / qe_ready / qe_advance
 QE_RD_SOFT, QE_RD_HARD, QE_RD_MUST_SYNC, QE_RD_SNAP, QE_RD_ENTS_CUT, QE_RD_APPLY_CUT = (
     1, 2, 4, 8, 16, 32)
@@ -513,6 +543,9 @@ PROTOTYPES = {
     "qe_replies_scratch_bytes": (C.c_size_t, [u64]),
     "qe_replies": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeRepliesIn),
                              C.POINTER(QeRepliesOut), vp, vp, vp]),
+    "qe_carry_scratch_bytes": (C.c_size_t, [u64]),
+    "qe_carry": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QePeers), C.POINTER(QeCarryIn),
+                           C.POINTER(QeCarryOut), vp, vp, vp]),
     "qe_ready_note": (C.c_int, [C.POINTER(QeProgress), C.POINTER(QeReadyState),
                                 C.POINTER(QeReadyNoteIn), vp]),
     "qe_ready_scratch_bytes": (C.c_size_t, [u64]),

@@ -17,6 +17,7 @@
 #include "qe_readstates.hpp"
 #include "qe_requests.hpp"
 #include "qe_applyconf.hpp"
+#include "qe_carry.hpp"
 
 namespace qe {
 
@@ -153,6 +154,26 @@ static size_t requests_scratch(void *scratch, RQArgs &a, ScanScratch &sd, ScanSc
   a.stop = c.take<uint32_t>(a.G);
   a.dflag = c.take<uint8_t>(a.n);
   a.okind = c.take<uint8_t>(a.n);
+  c.take<uint8_t>(2 * 64);
+  return c.at;
+}
+
+// qe_carry's scratch for a.G (the source's capacity) into `a`, `sl` (the local
+// list) and `sr` (the remote positions) -> its size: the chunk offsets of both
+// lists (u64), their chunk counts (u32), the count and remote flag bytes [a.G],
+// qe_collect's 64 B of slack per list.
+static size_t carry_scratch(void *scratch, CRArgs &a, ScanScratch &sl, ScanScratch &sr) {
+  Carve c{scratch};
+  const uint64_t nb = scan_chunks(a.G);
+  uint64_t *off = c.take<uint64_t>(2 * nb);
+  uint32_t *cnt = c.take<uint32_t>(2 * nb);
+  sl = {QE_OK, nb, off, cnt};
+  sr = {QE_OK, nb, off + nb, cnt + nb};
+  a.nb = nb;
+  a.offsets = sl.offsets;
+  a.counts = sl.counts;
+  a.kcnt = c.take<uint8_t>(a.G);
+  a.rflag = c.take<uint8_t>(a.G);
   c.take<uint8_t>(2 * 64);
   return c.at;
 }
@@ -1744,6 +1765,103 @@ int qe_requests(const qe_progress *p, const qe_follower *f, const qe_requests_in
   s = dispatch_requests_out(l, st);
   if (s) return s;
   return dispatch_route_positions({n, sd.nb, sd.offsets, a.dflag, out->deferred}, st);
+}
+
+size_t qe_carry_scratch_bytes(uint64_t capacity) {
+  CRArgs a{capacity};  // (G: the source's capacity)
+  ScanScratch sl, sr;
+  return carry_scratch(nullptr, a, sl, sr);
+}
+
+int qe_carry(const qe_progress *p, const qe_peers *peers, const qe_carry_in *in,
+             const qe_carry_out *out, void *scratch, uint64_t *stats, void *stream) {
+  const int rc = check_progress(p);
+  if (rc) return rc;
+  if (!peers || !in || !out || !peers->peer_group || !peers->peer_from) return QE_EINVAL;
+  if (in->reserved || out->reserved || (in->flags & ~QE_CARRY_SNAP_STATUS) ||
+      (in->ignore & ~QE_CARRY_TYPES))
+    return QE_EINVAL;
+  if (p->num_groups && p->stride < p->num_groups) return QE_EINVAL;
+  if (in->msg_runs > out->msg_runs || out->msg_runs > QE_MAX_MSG_RUNS) return QE_EINVAL;
+  if (!in->count || !out->count || !out->remote_count) return QE_EINVAL;
+  const uint64_t cap = in->capacity;
+  if (cap && (!in->group || !in->to || !in->type || !in->term || !in->index || !in->log_term ||
+              !out->disposition || !out->remote || !scratch))
+    return QE_EINVAL;
+  if (in->msg_runs && (!in->ent_len || !in->ent_term)) return QE_EINVAL;
+  if (out->base > out->capacity) return QE_EINVAL;
+  if (out->capacity &&
+      (!out->group || !out->from || !out->type || !out->term || !out->index || !out->log_term ||
+       !out->commit || !out->hint ||
+       (out->msg_runs && (!out->ent_len || !out->ent_term || out->ent_pitch < out->capacity))))
+    return QE_EINVAL;
+  if (!al(scratch, 8)) return QE_EINVAL;
+  if (cap > 0xFFFFFFF0ull) return QE_ERANGE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (cap == 0) {
+    const int s = hip_status(hipMemsetAsync(out->count, 0, sizeof(uint64_t), st));
+    return s ? s : hip_status(hipMemsetAsync(out->remote_count, 0, sizeof(uint64_t), st));
+  }
+  CRArgs a{};
+  a.G = cap;
+  a.ng = p->num_groups;
+  a.goff = p->group_offset;
+  a.stride = p->stride;
+  a.S = p->num_slots;
+  a.E_in = in->msg_runs;
+  a.E_out = out->msg_runs;
+  a.flags = in->flags;
+  a.ignore = in->ignore;
+  a.cut_wide = p->num_slots > 8;
+  a.peer_group = peers->peer_group;
+  a.peer_from = peers->peer_from;
+  a.icount = in->count;
+  a.group = in->group;
+  a.to = in->to;
+  a.type = in->type;
+  a.term = in->term;
+  a.index = in->index;
+  a.log_term = in->log_term;
+  a.commit = in->commit;
+  a.hint = in->hint;
+  a.ctx = in->ctx;
+  a.mflags = in->mflags;
+  a.ent_len = in->ent_len;
+  a.ent_term = in->ent_term;
+  a.drop = in->drop;
+  a.cut = in->cut;
+  a.ocap = out->capacity;
+  a.base = out->base;
+  a.pitch = out->ent_pitch;
+  a.o_group = out->group;
+  a.o_from = out->from;
+  a.o_type = out->type;
+  a.o_term = out->term;
+  a.o_index = out->index;
+  a.o_log_term = out->log_term;
+  a.o_commit = out->commit;
+  a.o_hint = out->hint;
+  a.o_ctx = out->ctx;
+  a.o_mflags = out->mflags;
+  a.o_ent_len = out->ent_len;
+  a.o_ent_term = out->ent_term;
+  a.o_src = out->src;
+  a.disposition = out->disposition;
+  a.stats = stats;
+  ScanScratch sl, sr;
+  carry_scratch(scratch, a, sl, sr);  // (cap is in range: its chunks fit a launch)
+  int s = dispatch_carry_classify(a, st);
+  if (s) return s;
+  s = dispatch_carry_count(a, st);
+  if (s) return s;
+  launch_count(a.rflag, cap, sr, st);
+  s = launch_scan(sl, out->count, st);
+  if (s) return s;
+  s = launch_scan(sr, out->remote_count, st);
+  if (s) return s;
+  s = dispatch_carry_fill(a, st);
+  if (s) return s;
+  return dispatch_route_positions({cap, sr.nb, sr.offsets, a.rflag, out->remote}, st);
 }
 
 int qe_stats_reduce(const uint64_t *stats, uint64_t *out, void *stream) {

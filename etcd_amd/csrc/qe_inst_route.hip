@@ -4,6 +4,7 @@
 // and the positions fill both deferred lists share.  None depends on the slot
 // count at compile time: one object, not one per QE_S.
 #define QE_ROUTE_KERNELS
+#define QE_ROUTE_POSITIONS_KERNEL
 #include "qe_inbox.hpp"
 #include "qe_requests.hpp"
 

@@ -38,8 +38,9 @@ struct RoutePos {
 // defined in qe_inst_route.hip
 int dispatch_route_positions(const RoutePos &a, hipStream_t st);
 
-// The kernels are defined in the one object that launches them, which sets
-// QE_ROUTE_KERNELS; qe_api.hip takes the argument structs and the dispatchers.
+// The kernels are defined in the objects that launch them, which set
+// QE_ROUTE_KERNELS (qe_inst_route.hip, qe_inst_carry.hip); qe_api.hip takes the
+// argument structs and the dispatchers.
 #ifdef QE_ROUTE_KERNELS
 
 // Record `lane` of tile t: its key, group (global and local), slot and type,
@@ -94,11 +95,14 @@ __device__ __forceinline__ void route_positions_tile(const RoutePos &a, uint64_t
              has ? pos * 4 : kOOB);
 }
 
-// The positions of the flagged records, ascending.
+// The positions of the flagged records, ascending: defined in the one object
+// that also sets QE_ROUTE_POSITIONS_KERNEL (qe_inst_route.hip).
+#ifdef QE_ROUTE_POSITIONS_KERNEL
 __global__ __launch_bounds__(kBlock) void k_route_positions(RoutePos a) {
   const int idx[1] = {QE_STAT_GROUPS};
   list_fill_walk<route_positions_tile>(a, idx, FlagCounts{a.flag});
 }
+#endif
 #endif  // QE_ROUTE_KERNELS
 
 }  // namespace qe

@@ -1556,6 +1556,126 @@ def inbox(ps, fol, ib, lm, sm, vm, pm, tick_action=None, stats=None):
     return ib
 
 
+class Peers(_Rows):
+    """The host's slot assignment as qe_carry reads it (qe_peers), resident:
+    peer_group [S][stride] int64 storage of the global id of the group that is
+    the peer in slot s of group g (QE_PEER_NONE: nobody), peer_from [S][stride]
+    u8 g's slot in that group's numbering.  A new table has no peer anywhere.
+    The scratch of carry() is cached here."""
+
+    FIELDS = "peer_group:u64 peer_from:u8"
+
+    def __init__(self, ps):
+        n = ps.S * ps.stride
+        self.peer_group = torch.full((n,), -1, dtype=torch.int64, device=ps.device)
+        self.peer_from = torch.full((n,), 0xFF, dtype=torch.uint8, device=ps.device)
+        self.scratch = None
+
+    @classmethod
+    def clusters(cls, ps, N):
+        """The static layout of N-node clusters: node i of cluster c is group
+        c * N + i of the batch and sits in slot i of every node of c, so the
+        peer in slot s < N of g is g - g % N + s and g's slot there is g % N.
+        Slots >= N, and the nodes a ragged last cluster lacks, have no peer."""
+        g = np.arange(ps.G, dtype=np.uint64)
+        pg = np.full((ps.S, ps.stride), _lib.QE_PEER_NONE, np.uint64)
+        pf = np.full((ps.S, ps.stride), 0xFF, np.uint8)
+        for s in range(min(int(N), ps.S)):
+            peer = g - g % np.uint64(N) + np.uint64(s)
+            ok = peer < ps.G
+            pg[s, :ps.G] = np.where(ok, np.uint64(ps.group_offset) + peer,
+                                    np.uint64(_lib.QE_PEER_NONE))
+            pf[s, :ps.G] = np.where(ok, g % np.uint64(N), 0xFF).astype(np.uint8)
+        return cls(ps).load_host(peer_group=pg, peer_from=pf)
+
+    def struct(self):
+        return _lib.QePeers(_ptr(self.peer_group), _ptr(self.peer_from))
+
+
+class Carried:
+    """What carry() leaves: `n` source records read, `count` local records
+    appended, `remote_count` records for receivers outside the batch;
+    `disposition` u8 [n] (QE_TD_*), `remote` int32 [remote_count] (their source
+    positions, ascending) and `src` int32 [count] (the source position of each
+    appended record) as device tensors; host() -> (disposition, remote) as
+    numpy arrays of the unsigned types."""
+
+    def __init__(self, n, count, remote_count, disposition, remote, src):
+        self.n, self.count, self.remote_count = n, count, remote_count
+        self.disposition, self.remote, self.src = disposition, remote, src
+
+    def host(self):
+        return (self.disposition.cpu().numpy(), self.remote.cpu().numpy().view(np.uint32))
+
+
+def _mask_arg(a, device):
+    """A torch tensor as it is, a numpy array uploaded (bool -> u8)."""
+    if a is None or isinstance(a, torch.Tensor):
+        return a
+    a = np.ascontiguousarray(a)
+    a = a.astype(np.uint8) if a.dtype == np.bool_ else a
+    return torch.from_numpy(a.view(_SIGNED.get(a.dtype, a.dtype)).copy()).to(device)
+
+
+def carry(ps, peers, src, ib, after=None, drop=None, cut=None, ignore=0, snap_status=True,
+          stats=None):
+    """qe_carry: the records an Outbox or a Replies `src` holds, carried to
+    their receivers by the Peers table and appended to the Inbox `ib` behind
+    its first `after` records (default ib.n), on the device: src's arrays and
+    its `count` are read where they are.  drop [>= src's length] u8 / bool
+    marks records that are lost, cut [G] mask-typed has bit s of cut[g] set
+    where the link g -> slot s is down, `ignore` has bit t set where records of
+    type t are lost; with snap_status every MsgSnap carried or lost here is
+    reported to its sender (QE_IMSG_SNAP_STATUS / _REJECT behind it).  The
+    Inbox keeps its ent rows at pitch n, so the two counts are read once (as
+    gather_deferred does).  Raises ValueError, ib.n unchanged, if the records
+    do not fit.  -> Carried."""
+    lib = _lib.lib()
+    after = ib.n if after is None else int(after)
+    E_in, E_out = int(getattr(src, "msg_runs", 0)), ib.msg_runs
+    if not 0 <= after <= ib.n or E_in > E_out:
+        raise ValueError("carry: `after` is past the Inbox's list, or src has more ent runs")
+    dev, cap = ps.device, src.capacity
+    room = max(0, ib.capacity - after)
+    r1 = max(1, room)
+    stage = {k: torch.empty(r1, dtype=getattr(ib, k).dtype, device=dev)
+             for k in ib.RECORD if getattr(ib, k) is not None}
+    ents = {k: torch.empty(E_out * r1, dtype=getattr(ib, k).dtype, device=dev)
+            for k in ("ent_len", "ent_term") if getattr(ib, k) is not None}
+    o_src = torch.empty(r1, dtype=torch.int32, device=dev)
+    disp = torch.empty(max(1, cap), dtype=torch.uint8, device=dev)
+    remote = torch.empty(max(1, cap), dtype=torch.int32, device=dev)
+    counts = torch.zeros(3, dtype=torch.int64, device=dev)  # local, remote, the source's
+    counts[2:3].copy_(src.count)
+    drop, cut = _mask_arg(drop, dev), _mask_arg(cut, dev)
+    if drop is not None and drop.numel() < cap:  # (the call reads it for i < n <= capacity)
+        drop = torch.cat([drop.to(torch.uint8), torch.zeros(cap - drop.numel(), dtype=torch.uint8,
+                                                            device=dev)])
+    _scratch(peers, dev, lib.qe_carry_scratch_bytes(cap))
+    i = _lib.QeCarryIn(cap, _ptr(src.count), E_in, _lib.QE_CARRY_SNAP_STATUS if snap_status else 0,
+                       _ptr(src.group), _ptr(src.to), _ptr(src.type), _ptr(src.term),
+                       _ptr(src.index), _ptr(src.log_term), _ptr(getattr(src, "commit", None)),
+                       _ptr(getattr(src, "hint", None)), _ptr(src.ctx),
+                       _ptr(getattr(src, "flags", None)), _ptr(getattr(src, "ent_len", None)),
+                       _ptr(getattr(src, "ent_term", None)), _ptr(drop), _ptr(cut), int(ignore), 0)
+    o = _lib.QeCarryOut(room, 0, r1, E_out, 0, _ptr(stage["group"]), _ptr(stage["from_"]),
+                        _ptr(stage["type"]), _ptr(stage["term"]), _ptr(stage["index"]),
+                        _ptr(stage["log_term"]), _ptr(stage["commit"]), _ptr(stage["hint"]),
+                        _ptr(stage.get("ctx")), _ptr(stage.get("flags")), _ptr(ents.get("ent_len")),
+                        _ptr(ents.get("ent_term")), _ptr(o_src), counts.data_ptr(), _ptr(disp),
+                        _ptr(remote), counts.data_ptr() + 8)
+    p, pe = ps.struct(), peers.struct()
+    check("qe_carry", lib.qe_carry(C.byref(p), C.byref(pe), C.byref(i), C.byref(o),
+                                   _ptr(peers.scratch), _ptr(stats), _stream(dev)))
+    count, remote_count, n = (int(x) for x in counts.cpu().numpy().view(np.uint64))
+    n = min(n, cap)
+    if count > room:
+        raise ValueError("the carried records do not fit the Inbox")
+    ib._put(after + count, after, {k: t[:count] for k, t in stage.items()},
+            {k: t.view(E_out, r1)[:, :count] for k, t in ents.items()})
+    return Carried(n, count, remote_count, disp[:n], remote[:remote_count], o_src[:count])
+
+
 class Requests(_Records):
     """The request list of qe_requests (qe_requests_in) for up to
     `list_capacity` records, its per-record outputs and its output list for up

@@ -542,8 +542,9 @@ typedef struct qe_peer_msgs {
  * qe_vote_step as a QE_VMSG_VOTE_RESP of that term with QE_VMF_REJECT
  * (becomeFollower(m.Term, None), QE_VR_STEPPED_DOWN: the same transition for
  * every response type).  MsgSnapStatus is local (term 0, node.ReportSnapshot):
- * the host's transport reports every MsgSnap it carried, or a peer whose
- * MsgSnap was lost stays in StateSnapshot. */
+ * whatever carries a MsgSnap reports it (qe_carry with QE_CARRY_SNAP_STATUS for
+ * the receivers in the batch, the host's transport for the others), or a peer
+ * whose MsgSnap was lost stays in StateSnapshot. */
 int qe_progress_step(const qe_progress *p, const qe_peer_msgs *m, uint64_t *stats,
                      void *stream);
 
@@ -1791,8 +1792,9 @@ int qe_outbox(const qe_progress *p, const qe_outbox_in *in, const qe_outbox_out 
  * qe_follower_step, qe_snapshot_step, qe_progress_step and qe_vote_step.
  *
  * The list is in delivery order; a record's position i is its rank.  Mapping
- * (sender group, `to` slot) to (receiver group, `from` slot) stays with the
- * transport, as slot assignment stays with the host.
+ * (sender group, `to` slot) to (receiver group, `from` slot) is the host's
+ * table (qe_peers), as slot assignment stays with the host; qe_carry applies it
+ * on the device for the receivers that share the batch.
  *
  *  1. Class.  QE_IMSG_APP and _HEARTBEAT are class F (qe_follower_step),
  *     QE_IMSG_SNAP is class S (qe_snapshot_step), QE_IMSG_APP_RESP ..
@@ -1965,7 +1967,8 @@ int qe_inbox(const qe_progress *p, const qe_follower *f, const qe_inbox_in *in,
  * MsgHeartbeatResp, Msg{Pre}VoteResp, Msg{Pre}Vote and MsgTimeoutNow records.
  * With qe_outbox and qe_inbox the loop tick -> step -> (outbox + replies) ->
  * transport -> inbox -> step moves no G-sized row to the host in either
- * direction.  It writes nothing resident.  Of p it reads num_groups (G),
+ * direction; where the receivers share the batch, qe_carry is that transport
+ * and no record leaves the device.  It writes nothing resident.  Of p it reads num_groups (G),
  * group_offset, num_slots (S), stride and, when the V family is given,
  * last_index, and nothing else.  A family is present iff its result row is
  * non-NULL; full = (1 << S) - 1.
@@ -2050,7 +2053,8 @@ int qe_inbox(const qe_progress *p, const qe_follower *f, const qe_inbox_in *in,
  * With this call duty H8 of a host (tests/cluster_sim.py), the vote half of H4
  * and the MsgTimeoutNow of a transfer are optional: the host copies
  * min(*count, capacity) records instead of the G-sized result rows it would
- * walk.  MsgSnapStatus (H11) stays the transport's. */
+ * walk.  MsgSnapStatus (H11) is reported by what carries the MsgSnap: qe_carry
+ * for a receiver in the batch, the host's transport otherwise. */
 #define QE_RMSG_BAD 255      /* a response whose `to` is no slot, or a GRANT / REJECT
                                 whose message type is no request */
 #define QE_STAT_REPLY_APP_RESP QE_STAT_VOTE_WON            /* qe_replies: records by type */
@@ -2092,6 +2096,146 @@ typedef struct qe_replies_out {
 size_t qe_replies_scratch_bytes(uint64_t num_groups);   /* == qe_collect_scratch_bytes */
 int qe_replies(const qe_progress *p, const qe_replies_in *in, const qe_replies_out *out,
                void *scratch, uint64_t *stats, void *stream);
+
+/* qe_carry (additive in ABI 8): a list of sent records -- a qe_outbox_out or a
+ * qe_replies_out list as it stands, `group` the sender and `to` a slot in the
+ * sender's numbering -- turned into the list the receivers' qe_inbox reads,
+ * `group` the receiver and `from` the sender's slot in the receiver's
+ * numbering.  It is the in-process `network` of the reference's tests
+ * (raft/raft_test.go:4633-4778): send maps m.To to a peer, filter (:4750-4774)
+ * drops by message type (ignorem), by directed link (dropm, cut, isolate) and by
+ * hook, and panics on a MsgHup.  Where the replicas of a group are co-resident
+ * in one batch, the loop step -> outbox / replies -> carry -> inbox -> step
+ * never leaves the device.  The mapping is the host's table, qe_peers: slot
+ * assignment stays with the host.  Of p the call reads num_groups (G),
+ * group_offset, num_slots (S) and stride and nothing else; it writes nothing
+ * resident.  n = min(*in->count, in->capacity) is read on the device, as
+ * qe_advance reads a list's length; the launches are sized by in->capacity.
+ *
+ * Per source record i < n, with g = group[i] - group_offset, in this order:
+ *  1. QE_TD_BAD.  type[i] outside {1..6, 10..15} (0, the local
+ *     QE_IMSG_SNAP_STATUS / _SNAP_STATUS_REJECT / _UNREACHABLE, QE_IMSG_HUP --
+ *     the reference's panic in filter -- and above, QE_OMSG_BAD / QE_RMSG_BAD
+ *     included); g >= G; to[i] >= S; peer_group[to*stride+g] == QE_PEER_NONE;
+ *     or the receiver is in the batch and peer_from[to*stride+g] >= S.  A BAD
+ *     record yields nothing.
+ *  2. QE_TD_LOST.  Bit type[i] of `ignore` is set, or drop[i] != 0, or bit
+ *     to[i] of cut[g] is set.  Only the SENDER's link bit is read: a two-way cut
+ *     is two bits, as network.cut is two drops.  A LOST record yields no
+ *     carried record.
+ *  3. QE_TD_REMOTE.  The receiver's id peer_group[to*stride+g] is outside
+ *     [group_offset, group_offset + G).  i goes into `remote`; nothing goes into
+ *     the local list and no status record: the transport that really carries
+ *     the record reports it.
+ *  4. QE_TD_LOCAL.  One local record: group = peer_group[to*stride+g], from =
+ *     peer_from[to*stride+g]; type, term, index, log_term, commit, hint, ctx and
+ *     mflags copied (0 where the source array is NULL); the ent rows j <
+ *     in->msg_runs copied, the rows in->msg_runs <= j < out->msg_runs 0.
+ *  5. MsgSnapStatus (duty H11; node.ReportSnapshot, raft/raft.go:1310-1331),
+ *     with QE_CARRY_SNAP_STATUS in in->flags.  A QE_IMSG_SNAP record that is
+ *     LOCAL is followed directly by a local record with group = group[i] (the
+ *     sender), from = to[i], type = QE_IMSG_SNAP_STATUS and term (a local
+ *     message) and every other field 0.  A QE_IMSG_SNAP record that is LOST
+ *     (wherever its receiver lives: the loss was decided here) yields that
+ *     record alone, with QE_IMSG_SNAP_STATUS_REJECT.  So a source record yields
+ *     0, 1 or 2 local records.
+ *  6. Order and truncation.  The local list is in source order, a status record
+ *     directly behind its MsgSnap; local record k goes to position base + k of
+ *     the qe_carry_out arrays, its ent rows to [j*ent_pitch + base + k].  A
+ *     local record at a position >= out->capacity is not written; *out->count
+ *     is still the full number of local records (it does not include base),
+ *     and nothing below base or at or past min(base + *count, capacity) is
+ *     touched.  src[k] (optional) = i, for a status record the i of its MsgSnap.
+ *     disposition[i] = QE_TD_* for i < n and is not touched at or past n;
+ *     remote[0 .. *remote_count) = the positions of the REMOTE records,
+ *     ascending.  Two calls chain: the second takes base = base + *count of the
+ *     first (read back once, or known from the capacities).
+ *  7. stats (optional): QE_STAT_CARRY_LOCAL / _REMOTE / _LOST / _BAD += source
+ *     records by disposition, BAD also into QE_STAT_INVARIANT_VIOLATIONS;
+ *     QE_STAT_CARRY_SNAP_STATUS += status records (both kinds); QE_STAT_GROUPS
+ *     += local records ASKED FOR (*out->count: those past capacity too);
+ *     QE_STAT_CHECKSUM += mix64(mix64(group[i] * 0x9E3779B97F4A7C15 ^
+ *     0x8CB92BA72F3D8DD7 ^ disposition << 56 ^ type << 48 ^ to << 40) ^ i) per
+ *     source record i < n.
+ * Every array, count included, is a DEVICE pointer; `cut` is mask-typed
+ * (qe_mask_bytes(S) bytes per group).  scratch is
+ * qe_carry_scratch_bytes(in->capacity) bytes of device memory, 8-B aligned: two
+ * bytes per record plus 2 * qe_collect_scratch_bytes(capacity).  Nothing in it
+ * is G-sized.  Stream-ordered, no host synchronisation: a classify pass, the
+ * count and scan of each of the two lists, the fill of the local list and the
+ * scatter of the remote positions.  No atomics but the statistics: the outputs
+ * are bit-exact from run to run.
+ * QE_ERANGE: in->capacity > 0xFFFFFFF0 (positions are 32-bit).
+ * QE_EINVAL: a NULL p / peers / in / out; num_slots outside 1..16 or a nonzero
+ * reserved field of p, in or out; stride < num_groups; a NULL peer_group /
+ * peer_from / in->count / out->count / out->remote_count; in->capacity > 0
+ * with a NULL in->group / to / type / term / index / log_term (commit, hint,
+ * ctx, mflags, drop and cut may be NULL), a NULL out->disposition / remote, or
+ * a NULL scratch; scratch not 8-B aligned; in->msg_runs > out->msg_runs or
+ * either > QE_MAX_MSG_RUNS; in->msg_runs > 0 with a NULL in->ent_len /
+ * ent_term; base > out->capacity; out->capacity > 0 with a NULL out->group /
+ * from / type / term / index / log_term / commit / hint (ctx, mflags and src may
+ * be NULL: not written) or, with out->msg_runs > 0, a NULL out->ent_len /
+ * ent_term or ent_pitch < capacity; `ignore` with a bit outside the carriable
+ * types {1..6, 10..15}; `flags` other than QE_CARRY_SNAP_STATUS.  Every
+ * argument check runs before the first HIP call.  in->capacity == 0 is QE_OK
+ * with *out->count = *out->remote_count = 0.
+ *
+ * With this call duty H11 of a host (tests/cluster_sim.py: Sim.snap_status) and
+ * the addressing half of Sim.send are optional for co-resident replicas.
+ * Duplication and delay are a schedule, the host's or the simulation's. */
+#define QE_PEER_NONE 0xFFFFFFFFFFFFFFFFull   /* no peer behind this slot */
+#define QE_CARRY_SNAP_STATUS 1u   /* in->flags: rule 5 */
+#define QE_CARRY_TYPES 0x0000FC7Eu /* the carriable types, as `ignore` bits */
+#define QE_TD_LOCAL 1             /* in the local list                        */
+#define QE_TD_REMOTE 2            /* the receiver is outside the batch        */
+#define QE_TD_LOST 3              /* ignorem / drop / cut                     */
+#define QE_TD_BAD 255
+#define QE_STAT_CARRY_LOCAL QE_STAT_VOTE_WON          /* qe_carry: records by disposition */
+#define QE_STAT_CARRY_LOST QE_STAT_VOTE_LOST
+#define QE_STAT_CARRY_REMOTE QE_STAT_VOTE_PENDING
+#define QE_STAT_CARRY_BAD QE_STAT_COMMIT_INF
+#define QE_STAT_CARRY_SNAP_STATUS QE_STAT_COMMIT_ADVANCED  /* ... status records made */
+
+typedef struct qe_peers {            /* resident, the host's slot assignment */
+  const uint64_t *peer_group;        /* [S][stride] global id of the group that is the peer in slot s of g */
+  const uint8_t  *peer_from;         /* [S][stride] g's slot in that group's numbering */
+} qe_peers;
+
+typedef struct qe_carry_in {         /* a qe_outbox_out or qe_replies_out list, as it stands */
+  uint64_t capacity;                 /* records the arrays hold; ent pitch */
+  const uint64_t *count;             /* DEVICE: n = min(*count, capacity), as qe_advance takes a list */
+  uint32_t msg_runs;                 /* E_in, 0..QE_MAX_MSG_RUNS */
+  uint32_t flags;                    /* QE_CARRY_SNAP_STATUS */
+  const uint64_t *group; const uint8_t *to, *type;
+  const uint64_t *term, *index, *log_term;
+  const uint64_t *commit;            /* or NULL = 0 (a replies list) */
+  const uint64_t *hint;              /* or NULL = 0 (an outbox list) */
+  const uint32_t *ctx; const uint8_t *mflags;   /* each or NULL = 0 */
+  const uint32_t *ent_len; const uint64_t *ent_term;  /* [E_in][capacity] */
+  const uint8_t  *drop;              /* [capacity] or NULL: nonzero = this record is lost (msgHook / a fractional dropm draw, the host's) */
+  const void     *cut;               /* [G] mask-typed or NULL: bit s of cut[g] = the link g -> slot s is down (dropm >= 1) */
+  uint32_t ignore;                   /* bit t set: records of type t are lost (ignorem) */
+  uint32_t reserved;                 /* must be 0 */
+} qe_carry_in;
+
+typedef struct qe_carry_out {        /* the local list is in qe_inbox_in's layout */
+  uint64_t capacity, base, ent_pitch; /* local record k goes to position base + k; ent rows at [j*ent_pitch + base + k] */
+  uint32_t msg_runs, reserved;       /* E_out >= E_in */
+  uint64_t *group; uint8_t *from, *type;
+  uint64_t *term, *index, *log_term, *commit, *hint;
+  uint32_t *ctx; uint8_t *mflags;    /* each or NULL: not written */
+  uint32_t *ent_len; uint64_t *ent_term;
+  uint32_t *src;                     /* or NULL: the source position of local record k (a status record: its MsgSnap's) */
+  uint64_t *count;                   /* DEVICE: local records asked for (may exceed capacity - base) */
+  uint8_t  *disposition;             /* [in.capacity] QE_TD_* for i < n */
+  uint32_t *remote;                  /* [in.capacity] positions of the REMOTE records, ascending */
+  uint64_t *remote_count;            /* DEVICE */
+} qe_carry_out;
+
+size_t qe_carry_scratch_bytes(uint64_t capacity);
+int qe_carry(const qe_progress *p, const qe_peers *peers, const qe_carry_in *in,
+             const qe_carry_out *out, void *scratch, uint64_t *stats, void *stream);
 
 /* qe_ready_note / qe_ready / qe_advance (additive in ABI 8): the storage half
  * of RawNode.Ready() as a dense device list, and the Advance() that moves the
